@@ -16,19 +16,29 @@ Multi-GPU (configs[3], stripe-local placement): each rank owns its own
 stripes (stripe s of the global job -> rank s mod N), no collective on the
 data path -> weak scaling.  The driver launches N>1 with torch.distributed.run.
 
-Also reported: the roofline of the dominant kernel (encode, HIP events on the
-launch stream) against the 8 TB/s HBM3E peak, and the CPU baseline (the
-oracle's ports of infectious's scalar and split-nibble addmul, 1 thread and
-all usable CPUs, on a bounded sample of the same workload, on rank 0 after
-the timed region at every N).  At N = 1 two more legs follow, never part of
-value: "config1" (configs[0], the reference's one-call-per-message pattern on
-the 1,048,580-byte blob, median latencies next to the oracle on one core) and
-"config5" (configs[4], RS(64,16) with 64 KiB shards, fresh 1-16 erasures).
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up,
+times the K steps and prints the line; the roofline of the dominant kernel
+(encode, HIP events on the launch stream of the timed steps themselves)
+against the 8 TB/s HBM3E peak is part of it.  `--dump-outputs DIR` writes a
+fixed, seeded sample of what the last timed step left in the caller's
+buffers as DIR/<name>.npy (output_dumper), so two builds can be compared
+output for output: the inputs are the same in every run with the same
+arguments.
+
+Everything else runs only with `--full`, after the timed region and never
+part of value: the CPU baseline (the oracle's ports of infectious's scalar
+and split-nibble addmul, 1 thread and all usable CPUs, on a bounded sample of
+the same workload, on rank 0 at N = 1), and at N = 1 the device-set leg and
+three more legs: "config1" (configs[0], the reference's one-call-per-message
+pattern on the 1,048,580-byte blob, median latencies next to the oracle on
+one core), "config5" (configs[4], RS(64,16) with 64 KiB shards, fresh 1-16
+erasures) and "config3_worst" (configs[2] with four data shards erased in
+every stripe).
 
 `--gpus N` with N > 1 and no launcher starts N ranks itself
 (torch.distributed.run as a child process, the JSON line relayed); under a
-launcher, WORLD_SIZE must equal --gpus.  At N > 1 the same ranks then run a
-short shard-distributed leg (configs[3]: the RCCL survivor gather and the
+launcher, WORLD_SIZE must equal --gpus.  With `--full` at N > 1 the same
+ranks then run a short shard-distributed leg (configs[3]: the RCCL survivor gather and the
 pointer-mode reconstruct, the last two steps checked on a sample) reported
 as "gather" -- never part of value.  A per-rank watchdog abandons a leg stuck
 in a collective: the headline line is still printed, then the ranks exit
@@ -60,6 +70,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything reported beside it: the CPU baseline, the "
+                         "device-set leg and the configs[0] / configs[4] / configs[2] worst-case legs at "
+                         "N = 1, the gather leg at N > 1.  A plain run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in the caller's buffers "
+                         "as DIR/<name>.npy (float32; a fixed, seeded sample of the parity buffer, the data "
+                         "buffer and the shards the last reconstruct regenerated)")
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--n", type=int, default=14)
     ap.add_argument("--shard", type=int, default=1 << 20, help="shard bytes S")
@@ -78,7 +97,7 @@ def parse():
     ap.add_argument("--erase", default=None,
                     help="fixed erased shard ids for every stripe, e.g. 0,1,2,3 (default random)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the CPU baseline sample, timed on rank 0 at N = 1 only (0 disables)")
+                    help="--full: budget of the CPU baseline sample, timed on rank 0 at N = 1 only (0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this job may use (affinity and cgroup quota)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
@@ -90,7 +109,7 @@ def parse():
     ap.add_argument("--chunks", type=int, default=8,
                     help="sharded placement: exchange chunks per step (two chunks' buffers live)")
     ap.add_argument("--gather-stripes", type=int, default=512,
-                    help="N > 1, local placement: after the timed region (and the CPU baseline), "
+                    help="--full, N > 1, local placement: after the timed region, "
                          "a short shard-distributed leg with this many owned stripes per rank "
                          "runs the RCCL survivor gather + pointer reconstruct and checks it "
                          "(configs[3]); reported as 'gather', never 'value'. 0 disables")
@@ -98,12 +117,12 @@ def parse():
                     help="seconds after which a stuck gather leg is abandoned (the line is still printed, "
                          f"then the ranks exit {EXIT_GATHER_ABANDONED})")
     ap.add_argument("--device-set-stripes", type=int, default=512,
-                    help="N = 1: stripes per member of the device-set leg (a child process: one rs_new_devices "
+                    help="--full, N = 1: stripes per member of the device-set leg (a child process: one rs_new_devices "
                          "context over every visible GPU, [0, 0] on a one-GPU box; never value); 0 skips")
     ap.add_argument("--device-set-timeout", type=float, default=240.0)
     ap.add_argument("--device-set-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extra-legs", dest="extra_legs", action="store_false",
-                    help="N = 1: skip the configs[0] (per-message latency), configs[4] (RS(64,16)) and "
+                    help="--full, N = 1: skip the configs[0] (per-message latency), configs[4] (RS(64,16)) and "
                          "configs[2] worst-case legs reported beside the headline")
     ap.add_argument("--config1-reps", type=int, default=200)
     ap.add_argument("--config5-stripes", type=int, default=16384)
@@ -111,7 +130,10 @@ def parse():
     ap.add_argument("--config5-warmup", type=int, default=2)
     ap.add_argument("--config3-steps", type=int, default=3,
                     help="N = 1: steps of the configs[2] worst-case leg (4 data erasures in every stripe; 0 skips)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.stream or args.placement == "sharded"):
+        ap.error("--dump-outputs covers the device-resident headline path (not --stream / --placement sharded)")
+    return args
 
 
 def erasure_sets(rng, count, stripes, n, emin, emax, pool=0):
@@ -312,7 +334,7 @@ def self_launch(gpus: int, argv) -> int:
 
 
 def device_run(f, k, n, S, stripes, steps, warmup, ersets, do_enc, do_rec, dev, seed=0x5EED,
-               prepare_emax=None, distributed=False):
+               prepare_emax=None, distributed=False, dump=None):
     """The device-resident hot path: `stripes` stripes of RS(k, n) with
     S-byte shards allocated and filled in HBM (splitmix64, untimed), then
     `warmup` untimed and `steps` timed steps, each = rs_encode_stripes of
@@ -321,7 +343,9 @@ def device_run(f, k, n, S, stripes, steps, warmup, ersets, do_enc, do_rec, dev, 
     Timed region bracketed by synchronize (+ barrier when distributed); HIP
     events on the launch stream time each kernel.  The buffers are freed
     before returning.  When every pattern of <= prepare_emax erasures fits
-    the ctx cache they are built before timing (prep_ms)."""
+    the ctx cache they are built before timing (prep_ms).  `dump`, if given,
+    is called after the timed region as dump(data, parity, erasure flags of
+    the last timed step) while the buffers still hold that step's output."""
     m = n - k
     stream = torch.cuda.current_stream(dev)
     sh = stream.cuda_stream
@@ -373,10 +397,63 @@ def device_run(f, k, n, S, stripes, steps, warmup, ersets, do_enc, do_rec, dev, 
     elapsed = time.perf_counter() - t0
     res = {"elapsed": elapsed, "encode_ms": [a.elapsed_time(b) for a, b, _ in ev],
            "reconstruct_ms": [b.elapsed_time(c) for _, b, c in ev], "prep_ms": prep_ms}
+    if dump is not None:
+        dump(data, parity, ersets[warmup + steps - 1] if do_rec else None)
     del data, parity
     torch.cuda.synchronize(dev)
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_ROWS = 512      # sampled shards per dumped array
+DUMP_WINDOW = 4096   # bytes taken from each sampled shard
+
+
+def output_dumper(out_dir, k, n, S, stripes, suffix="", seed=0xD0C5):
+    """The `dump` callback of device_run for --dump-outputs: writes a fixed
+    sample (numpy Generator seeded with `seed`, so the same bytes are picked
+    in every run with the same arguments) of what the last timed step left
+    in the caller's buffers as out_dir/<name><suffix>.npy, float32:
+      parity         the parity buffer rs_encode_stripes fills,
+      data           the data buffer rs_reconstruct_stripes repairs in place,
+      reconstructed  shards flagged erased in the last timed step, that is
+                     the bytes that step's reconstruct regenerated.
+    Each array is up to DUMP_ROWS shards x DUMP_WINDOW bytes (a window at a
+    sampled 16-byte aligned offset of each sampled shard): 8 MB an array."""
+    m = n - k
+    win = min(DUMP_WINDOW, S)
+
+    def sample(rng, buf, per, picks):
+        """picks: (stripe, shard index within buf's stripes) rows."""
+        rows = np.empty((len(picks), win), dtype=np.float32)
+        offs = rng.integers(0, (S - win) // 16 + 1, size=len(picks)) * 16
+        view = buf.view(stripes, per, S)
+        for r, ((s, i), o) in enumerate(zip(picks, offs)):
+            rows[r] = view[int(s), int(i), int(o):int(o) + win].cpu().numpy()
+        return rows
+
+    def pick(rng, cand):
+        cand = np.asarray(cand, dtype=np.int64).reshape(-1, 2)
+        take = rng.choice(len(cand), size=min(DUMP_ROWS, len(cand)), replace=False)
+        return cand[np.sort(take)]
+
+    def grid(per):
+        return np.stack(np.meshgrid(np.arange(stripes), np.arange(per), indexing="ij"), axis=-1)
+
+    def dump(data, parity, erased):
+        os.makedirs(out_dir, exist_ok=True)
+        rng = np.random.default_rng(seed)
+        np.save(os.path.join(out_dir, f"parity{suffix}.npy"), sample(rng, parity, m, pick(rng, grid(m))))
+        np.save(os.path.join(out_dir, f"data{suffix}.npy"), sample(rng, data, k, pick(rng, grid(k))))
+        if erased is not None:
+            picks = pick(rng, np.argwhere(erased))
+            rows = np.empty((len(picks), win), dtype=np.float32)
+            dpart = picks[picks[:, 1] < k]
+            ppart = picks[picks[:, 1] >= k] - [0, k]
+            rows[:len(dpart)] = sample(rng, data, k, dpart)
+            rows[len(dpart):] = sample(rng, parity, m, ppart)
+            np.save(os.path.join(out_dir, f"reconstructed{suffix}.npy"), rows)
+    return dump
 
 
 def guarded_leg(fn):
@@ -934,8 +1011,11 @@ def main():
     enc_bytes = stripes * (k + m) * S
     do_enc = args.mode in ("both", "encode")
     do_rec = args.mode in ("both", "reconstruct")
+    dump = None
+    if args.dump_outputs:
+        dump = output_dumper(args.dump_outputs, k, n, S, stripes, suffix=f"_rank{rank}" if world > 1 else "")
     run = device_run(f, k, n, S, stripes, args.steps, args.warmup, ersets, do_enc, do_rec, dev,
-                     seed=0x5EED ^ (rank << 32), prepare_emax=emax, distributed=distributed)
+                     seed=0x5EED ^ (rank << 32), prepare_emax=emax, distributed=distributed, dump=dump)
     elapsed, enc_ms, rec_ms, prep_ms = run["elapsed"], run["encode_ms"], run["reconstruct_ms"], run["prep_ms"]
     # Per-rank wall time, kernel times and algorithmic bytes (each rank draws
     # its own erasure sets, so its reconstruct bytes are its own); the job's
@@ -977,7 +1057,7 @@ def main():
     out = None
     if rank == 0:
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:  # after the timed region, rank 0 at N = 1 only
+        if args.full and args.cpu_seconds > 0 and world == 1:  # after the timed region, rank 0 at N = 1 only
             cpu = cpu_baseline(k, n, S, args.cpu_seconds, args.cpu_threads)
         out = {
             "metric": "RS(10,4) encode+reconstruct GB/s at 1/8 GPUs; % HBM roofline",
@@ -1039,7 +1119,7 @@ def main():
                           "encode_ms": round(v[1], 3), "reconstruct_ms": round(v[2], 3)}
                          for r, v in enumerate(per_rank)],
         }
-    if args.device_set_stripes > 0 and world == 1 and args.extra_legs:
+    if args.full and args.device_set_stripes > 0 and world == 1 and args.extra_legs:
         # The device-set context over every GPU a process sees (N = 1 only:
         # all of a node's GPUs are visible to it), in a child process, so a
         # fault or hang there (its peer reads have never run on an 8-GPU
@@ -1048,12 +1128,12 @@ def main():
         torch.cuda.empty_cache()
         out["device_set"] = device_set_child(args, k, n, S)
         f = rsmi.FEC(k, n, device=local)
-    if distributed and world > 1 and args.gather_stripes > 0:
+    if args.full and distributed and world > 1 and args.gather_stripes > 0:
         # configs[3]'s survivor gather on the same ranks, after the headline
         # is measured (device_run freed its buffers).
         gather_leg(args, f, k, n, S, emax, world, rank, dev, out)  # emits the line and tears down
         return
-    if rank == 0 and world == 1 and args.extra_legs:
+    if args.full and rank == 0 and world == 1 and args.extra_legs:
         # The reference's own per-message path (configs[0]) and the wide code
         # (configs[4]) at N = 1: reported beside the headline, never in value.
         del f

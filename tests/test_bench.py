@@ -202,6 +202,79 @@ def test_extra_leg_flags(monkeypatch):
     assert not a.extra_legs and a.config5_stripes == 64
 
 
+def test_full_and_dump_flags(monkeypatch):
+    """A plain run carries neither: the legs beside the headline wait for
+    --full, and --dump-outputs belongs to the device-resident headline path."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    for extra in (["--stream"], ["--placement", "sharded"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "out"] + extra)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def _dump_case(seed):
+    import torch
+    k, n, S, stripes = 4, 6, 8192, 300
+    rng = np.random.default_rng(seed)
+    data = torch.from_numpy(rng.integers(0, 256, size=stripes * k * S, dtype=np.uint8))
+    parity = torch.from_numpy(rng.integers(0, 256, size=stripes * (n - k) * S, dtype=np.uint8))
+    erased = bench.erasure_sets(rng, 1, stripes, n, 2, 2)[0]  # 600 erased shards >= DUMP_ROWS
+    return k, n, S, stripes, data, parity, erased
+
+
+def test_output_dumper_sample_is_fixed_and_comes_from_the_buffers(tmp_path):
+    """--dump-outputs: float32 arrays of DUMP_ROWS windows, the same positions
+    in every run (two dumps of the same buffers are equal), every
+    reconstructed row taken from a shard flagged erased."""
+    k, n, S, stripes, data, parity, erased = _dump_case(5)
+    for d in ("a", "b"):
+        bench.output_dumper(str(tmp_path / d), k, n, S, stripes)(data, parity, erased)
+    arrs = {}
+    for name in ("parity", "data", "reconstructed"):
+        x, y = (np.load(tmp_path / d / f"{name}.npy") for d in ("a", "b"))
+        assert x.dtype == np.float32 and x.shape == (bench.DUMP_ROWS, bench.DUMP_WINDOW)
+        assert np.array_equal(x, y)
+        arrs[name] = x
+    assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+    # every sampled row is a window of its buffer (found by searching the shards)
+    shards = {"parity": parity.numpy().reshape(-1, S), "data": data.numpy().reshape(-1, S)}
+    for name in ("parity", "data"):
+        row = arrs[name][7].astype(np.uint8)
+        assert any(row.tobytes() in sh.tobytes() for sh in shards[name])
+    full = np.concatenate([data.numpy().reshape(stripes, k, S), parity.numpy().reshape(stripes, n - k, S)], axis=1)
+    lost = full[erased.astype(bool)]
+    for r in (0, bench.DUMP_ROWS // 2, bench.DUMP_ROWS - 1):
+        row = arrs["reconstructed"][r].astype(np.uint8).tobytes()
+        assert any(row in sh.tobytes() for sh in lost)
+    # encode-only runs have no reconstructed array
+    bench.output_dumper(str(tmp_path / "c"), k, n, S, stripes)(data, parity, None)
+    assert sorted(os.listdir(tmp_path / "c")) == ["data.npy", "parity.npy"]
+
+
+def test_output_dumper_takes_everything_of_a_small_output(tmp_path):
+    """With fewer shards than DUMP_ROWS and shards no longer than DUMP_WINDOW
+    the dump is the whole output, in buffer order; the reconstructed rows are
+    the erased data shards, then the erased parity shards."""
+    import torch
+    k, n, S, stripes = 4, 6, 256, 9
+    rng = np.random.default_rng(11)
+    d = rng.integers(0, 256, size=(stripes, k, S), dtype=np.uint8)
+    p = rng.integers(0, 256, size=(stripes, n - k, S), dtype=np.uint8)
+    erased = bench.erasure_sets(rng, 1, stripes, n, 1, 2)[0]
+    bench.output_dumper(str(tmp_path), k, n, S, stripes, suffix="_rank3")(
+        torch.from_numpy(d.reshape(-1)), torch.from_numpy(p.reshape(-1)), erased)
+    assert np.array_equal(np.load(tmp_path / "data_rank3.npy"), d.reshape(-1, S).astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "parity_rank3.npy"), p.reshape(-1, S).astype(np.float32))
+    e = erased.astype(bool)
+    want = np.concatenate([d[e[:, :k]], p[e[:, k:]]]).astype(np.float32)
+    assert np.array_equal(np.load(tmp_path / "reconstructed_rank3.npy"), want)
+
+
 def test_guarded_leg_reports_failures():
     assert bench.guarded_leg(lambda: {"status": "ok"}) == {"status": "ok"}
     r = bench.guarded_leg(lambda: 1 / 0)

@@ -1,13 +1,15 @@
 """bench.py end to end on the GPU, as child processes (the way the driver
 runs it), at small sizes:
 
-* N = 2 under the gloo rehearsal backend (two ranks sharing cuda:0): the
+* a plain N = 1 run: the headline line alone, and --dump-outputs checked
+  against the oracle;
+* --full, N = 2 under the gloo rehearsal backend (two ranks sharing cuda:0): the
   self-launch, the stripe-local headline with per-rank bytes (no CPU
   baseline: it is timed at N = 1 only), and the configs[3] gather leg -- survivors exchanged between the
   ranks on a communication stream, reconstructed through rs_reconstruct_ptrs
   and checked against locally re-encoded stripes over the last two timed
   steps (the step whose receive slots the next step reused, and the last);
-* N = 1 with rank 0's CPU baseline and the configs[0] (per-message latency, checked against the oracle
+* --full, N = 1 with rank 0's CPU baseline and the configs[0] (per-message latency, checked against the oracle
   inside the leg) and configs[4] (RS(64,16)) legs.
 
 The driver's 8-GPU run uses RCCL instead of gloo; everything else is this
@@ -36,7 +38,7 @@ def _run(args, env_extra=None, timeout=240):
 
 @pytest.mark.gpu
 def test_bench_two_ranks_gloo_with_gather_leg(torch_dev):
-    d = _run(["--gpus", "2", "--stripes", "64", "--shard", "65536", "--steps", "2", "--warmup", "1",
+    d = _run(["--full", "--gpus", "2", "--stripes", "64", "--shard", "65536", "--steps", "2", "--warmup", "1",
               "--cpu-seconds", "0.5", "--gather-stripes", "16", "--gather-timeout", "150"],
              {"RSMI_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and len(d["per_rank"]) == 2
@@ -56,8 +58,44 @@ def test_bench_two_ranks_gloo_with_gather_leg(torch_dev):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(torch_dev, tmp_path):
+    """A plain run times its steps and prints the line -- no leg beside the
+    headline -- and --dump-outputs writes what the last timed step left in the
+    buffers.  At this size (240 data and 96 parity shards of one window) the
+    sample is the whole output, so it is checked byte for byte against the
+    oracle on the inputs the arguments fix: the splitmix64 data (seed 0x5EED),
+    its parity, and the shards the last step's erasure set (bench.py's
+    generator and seed) names."""
+    import numpy as np
+
+    import bench
+    from oracle import oracle
+    k, n, S, stripes, steps, warmup = 10, 14, 4096, 24, 2, 1
+    d = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--stripes", str(stripes),
+              "--shard", str(S), "--dump-outputs", str(tmp_path)])
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GB/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["roofline"]["frac"] > 0
+    assert d["cpu_baseline"] is None
+    assert not {"config1", "config5", "config3_worst", "device_set", "gather"} & set(d)
+    assert sorted(os.listdir(tmp_path)) == ["data.npy", "parity.npy", "reconstructed.npy"]
+    got = {name: np.load(tmp_path / f"{name}.npy") for name in ("data", "parity", "reconstructed")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    data = oracle.splitmix_bytes(stripes * k * S, 0x5EED)
+    E = oracle.fec_matrix(k, n)
+    parity = np.concatenate([np.frombuffer(oracle.encode(E, k, n, data[s * k * S:(s + 1) * k * S].tobytes()),
+                                           dtype=np.uint8) for s in range(stripes)])
+    data, parity = data.reshape(stripes, k, S), parity.reshape(stripes, n - k, S)
+    assert np.array_equal(got["data"], data.reshape(-1, S).astype(np.float32))
+    assert np.array_equal(got["parity"], parity.reshape(-1, S).astype(np.float32))
+    e = bench.erasure_sets(np.random.default_rng(0xE4A5), warmup + steps, stripes, n, 1, n - k)[-1].astype(bool)
+    want = np.concatenate([data[e[:, :k]], parity[e[:, k:]]]).astype(np.float32)
+    assert np.array_equal(got["reconstructed"], want)
+
+
+@pytest.mark.gpu
 def test_bench_single_gpu_extra_legs(torch_dev):
-    d = _run(["--stripes", "64", "--shard", "65536", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2",
+    d = _run(["--full", "--stripes", "64", "--shard", "65536", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2",
               "--config1-reps", "3", "--config5-stripes", "64", "--config5-steps", "2", "--config5-warmup", "1",
               "--config3-steps", "2", "--device-set-stripes", "24"])
     assert d["n_gpus"] == 1 and d["roofline"]["frac"] > 0

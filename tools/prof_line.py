@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Summarise rocprofv3 passes of ONE default bench.py line (headline +
-config1 + config5 legs; tools/gpu/r04*.sh layout):
+"""Summarise rocprofv3 passes of ONE default `bench.py --full` line (headline
++ config1 + config5 legs; tools/gpu/r04*.sh layout):
 
   <dir>/trace/run_kernel_trace.csv   --kernel-trace --stats
   <dir>/fetch/run_counter_collection.csv, <dir>/write/...   --pmc FETCH_SIZE / WRITE_SIZE (optional)
@@ -169,7 +169,7 @@ def main():
         fh.write("\n".join(lines) + "\n")
     if a.traffic_json and traffic:
         out = {"_note": "per-launch HBM traffic (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE, the gfx950 correction) and "
-                        "kernel-trace time of each role of one default bench.py line, keyed by role and workload; "
+                        "kernel-trace time of each role of one default bench.py --full line, keyed by role and workload; "
                         "bench.py copies the entry of its dominant kernel into roofline.traffic / traffic_source. "
                         "Written by tools/prof_line.py.",
                "entries": traffic}
