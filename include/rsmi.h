@@ -71,9 +71,10 @@ int rs_device(const rs_ctx *ctx);
 /* Copy of the n x k row-major encode matrix (infectious FEC.enc_matrix). */
 int rs_encode_matrix(const rs_ctx *ctx, uint8_t *out);
 const char *rs_strerror(int status);
-/* Diagnostics: name of the kernel that serves encode (which = 0) or
- * reconstruct (which = 1) for this ctx, e.g. "bitslice_k64_m16" or
- * "K10_MG4_B256" (no reference counterpart). */
+/* Diagnostics: name of the kernel that serves encode (which = 0),
+ * reconstruct (which = 1) or verify (which = 2) for this ctx, e.g.
+ * "bitslice_k64_m16", "K10_MG4_B256" or "verify_K10_MG4_B256" (no reference
+ * counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -163,6 +164,36 @@ int rs_reconstruct_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride,
                            void *parity, size_t parity_stripe_stride, size_t shard_pitch,
                            size_t shard_len, size_t stripes, const uint8_t *erased,
                            void *stream);
+
+#define RS_VERIFY_CLEAN 0xFFFFFFFFu
+
+/* Device-resident consistency check (the check half of infectious Correct,
+ * stripe-batched).  Layout and argument rules as rs_encode_stripes.
+ * first_bad: DEVICE array of `stripes` uint32, 4-byte aligned.
+ * first_bad[s] = the lowest byte offset o < shard_len at which any stored
+ * parity shard of stripe s differs from the parity recomputed from its k data
+ * shards, or RS_VERIFY_CLEAN.
+ * Reads data and parity only; writes nothing but first_bad.
+ * Bytes at offsets >= shard_len (padding to 16, pitch gaps) are not compared.
+ * Enqueued on stream; returns when queued. */
+int rs_verify_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride,
+                      const void *parity, size_t parity_stripe_stride, size_t shard_pitch,
+                      size_t shard_len, size_t stripes, uint32_t *first_bad, void *stream);
+
+/* Scrub: verify, locate the corrupt shards of every inconsistent stripe,
+ * regenerate them in place, verify again.
+ * Repairs every stripe in which at most floor(m/2) shards (data or parity)
+ * hold wrong bytes, however many bytes and wherever in those shards.
+ * status (HOST, int[stripes], may be NULL): RS_OK or RS_ETOO_MANY_ERRORS per stripe.
+ * rewritten (HOST, uint8_t[stripes*n], may be NULL): non-zero where shard i of
+ * stripe s was regenerated.  For a stripe that ends RS_ETOO_MANY_ERRORS these
+ * are the shards whose contents were replaced.
+ * Synchronous: returns after the last verify has completed on stream.
+ * Returns RS_OK if every stripe ends consistent, else RS_ETOO_MANY_ERRORS
+ * (or an argument/device/memory error, in which case nothing is promised). */
+int rs_correct_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                       size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                       size_t stripes, int *status, uint8_t *rewritten, void *stream);
 
 /* rs_reconstruct_ptrs: rs_reconstruct_stripes with shards anywhere in
  * device memory.  shard_ptrs is a DEVICE array [stripes][n] of device
@@ -300,6 +331,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    contiguous ranges (rs_partition), each range on its member's thread, all
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
+ *    rs_verify_stripes, rs_correct_stripes,
  *    rs_reconstruct_ptrs, rs_fill_splitmix, rs_blake2b_device) run on a
  *    member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs

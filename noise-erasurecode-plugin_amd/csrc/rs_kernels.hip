@@ -128,8 +128,15 @@ __device__ __forceinline__ void step_fence(uint32_t (&acc)[kRowsPerStep][4]) {
 // MG output rows: logical block `blk` of `nblk` (rs_matmul_kernel: blockIdx.x
 // of the grid; rs_resident_kernel: each job's blocks in turn).  LDS: [k][MG/4][20]
 // table dwords | k survivor pointers.
-template <int K, int MG, int BT, bool NT>
-__device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uint32_t nblk, uint4* lds4) {
+//
+// VF (verify twin, rs_verify_kernel): the block reads the stored 16-byte
+// columns of its output rows instead of writing them.  They are requested
+// next to the survivor loads and become the accumulators' initial value, so
+// after the MACs an accumulator holds stored ^ recomputed and any set bit is
+// a mismatch; nothing is stored but one atomicMin per wave that saw one.
+template <int K, int MG, int BT, bool NT, bool VF = false>
+__device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uint32_t nblk, uint4* lds4,
+                                             uint32_t* first_bad = nullptr, uint32_t shard_len = 0) {
     static_assert(MG % 2 == 0, "MG must be even");
     constexpr int TG = (MG + kRowsPerStep - 1) / kRowsPerStep;  // sub-steps per survivor
     constexpr int RL = MG - (TG - 1) * kRowsPerStep;            // rows in the last sub-step
@@ -260,6 +267,24 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
                                      : pbase + static_cast<uint64_t>(oid[r] - a.k) * a.pitch;
         }
     }
+    uint32_t acc[TG][kRowsPerStep][4];
+    // Verify: the accumulators start as the stored columns, loaded next to
+    // the survivors so they ride the same latency.  Rows past eg are not
+    // read and stay zero (their tables are zero too, so they never report).
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                uint4 p = make_uint4(0u, 0u, 0u, 0u);
+                if (g * kRowsPerStep + r < eg) p = gload16<NT>(dp[g * kRowsPerStep + r] + at);
+                acc[g][r][0] = p.x;
+                acc[g][r][1] = p.y;
+                acc[g][r][2] = p.z;
+                acc[g][r][3] = p.w;
+            }
+    };
+    if constexpr (VF) load_stored(off0);
     // Split tables of rows [row0, row0 + MG): sub-step (j, g) holds rows
     // 4g..4g+3 as 4 x 5 dwords.
     if (one_coef) {
@@ -284,13 +309,14 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
         const bool ok = col <= last;
         // Tail lanes re-read the last column (always in bounds) and skip the store.
         const uint32_t off = (ok ? col : last) * 16u;
-        uint32_t acc[TG][kRowsPerStep][4];
+        if constexpr (!VF) {
 #pragma unroll
-        for (int g = 0; g < TG; ++g)
+            for (int g = 0; g < TG; ++g)
 #pragma unroll
-            for (int r = 0; r < kRowsPerStep; ++r)
+                for (int r = 0; r < kRowsPerStep; ++r)
 #pragma unroll
-                for (int w = 0; w < 4; ++w) acc[g][r][w] = 0u;
+                    for (int w = 0; w < 4; ++w) acc[g][r][w] = 0u;
+        }
         // Row groups of 4 beyond the pattern's outputs are skipped (uniform).
         const int tg_used = (eg + kRowsPerStep - 1) / kRowsPerStep;
 
@@ -339,14 +365,65 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
                 for (int j = 0; j < K; ++j) xpre[j] = gload16<NT>(sp[j] + noff);
             }
         }
+        if constexpr (VF) {
+            // Bytes at which any row's stored column differs from the
+            // recomputed one; tail lanes and bytes past shard_len do not count.
+            uint32_t d[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int g = 0; g < TG; ++g)
+            for (int g = 0; g < TG; ++g)
 #pragma unroll
-            for (int r = 0; r < kRowsPerStep; ++r) {
-                const int t = g * kRowsPerStep + r;
-                if (t >= eg) break;
-                if (ok) gstore16<NT>(dp[t] + off, make_uint4(acc[g][r][0], acc[g][r][1], acc[g][r][2], acc[g][r][3]));
+                for (int r = 0; r < kRowsPerStep; ++r)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) d[w] |= acc[g][r][w];
+            const uint32_t nb = ok ? min(16u, shard_len - col * 16u) : 0u;  // bytes of this column below shard_len
+            uint32_t byte = 16u;
+#pragma unroll
+            for (int w = 3; w >= 0; --w) {
+                const uint32_t nbw = nb > 4u * w ? min(4u, nb - 4u * w) : 0u;
+                const uint32_t dw = d[w] & (nbw >= 4u ? ~0u : (1u << (8u * nbw)) - 1u);
+                if (dw) byte = 4u * w + (static_cast<uint32_t>(__builtin_ctz(dw)) >> 3);
             }
+            // Lanes are in column order: the first mismatching lane holds the
+            // wave's lowest offset.
+            const bool bad = byte < 16u;
+            const uint64_t bal = __ballot(bad);
+            if (bad && (bal & ((1ull << __lane_id()) - 1ull)) == 0) atomicMin(&first_bad[s], col * 16u + byte);
+            if (it + 1 < a.iters && colbase + cstride < a.ncols16) {
+                const uint32_t ncol = colbase + cstride + threadIdx.x;
+                load_stored((ncol <= last ? ncol : last) * 16u);
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < TG; ++g)
+#pragma unroll
+                for (int r = 0; r < kRowsPerStep; ++r) {
+                    const int t = g * kRowsPerStep + r;
+                    if (t >= eg) break;
+                    if (ok) gstore16<NT>(dp[t] + off, make_uint4(acc[g][r][0], acc[g][r][1], acc[g][r][2], acc[g][r][3]));
+                }
+        }
+    }
+}
+
+// Verify twin of rs_matmul_kernel: first_bad[stripe] = min(first_bad[stripe],
+// lowest mismatching byte offset below shard_len); the caller presets
+// first_bad to 0xFF bytes on the same stream.
+template <int K, int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_verify_kernel(MatArgs a, uint32_t* first_bad, uint32_t shard_len) {
+    extern __shared__ uint4 lds4[];
+    matmul_block<K, MG, BT, NT, true>(a, blockIdx.x, gridDim.x, lds4, first_bad, shard_len);
+}
+
+// Scrub's locate step: wave i copies the n bytes of stripe pairs[i].x at byte
+// offset pairs[i].y, one per shard in id order, to out[i * n .. i * n + n).
+__global__ __launch_bounds__(64) void gather_columns_kernel(const uint8_t* data, const uint8_t* parity,
+                                                            uint64_t data_ss, uint64_t parity_ss, uint64_t pitch,
+                                                            uint32_t k, uint32_t n, const uint2* pairs, uint8_t* out) {
+    const uint2 p = pairs[blockIdx.x];
+    for (uint32_t id = threadIdx.x; id < n; id += 64u) {
+        const uint8_t* shard = id < k ? data + p.x * data_ss + static_cast<uint64_t>(id) * pitch
+                                      : parity + p.x * parity_ss + static_cast<uint64_t>(id - k) * pitch;
+        out[static_cast<size_t>(blockIdx.x) * n + id] = shard[p.y];
     }
 }
 
@@ -518,9 +595,30 @@ const Variant& pick(int k, int rows) {
     return kVariants[0];  // unreachable: both runtime-k variants are listed
 }
 
+// Verify twins of the variants that serve an encode; every other (k, m)
+// goes through row groups of the runtime-k ones.
+struct VerifyVariant {
+    int K, MG;
+    const char* name;
+    void (*fn)(MatArgs, uint32_t*, uint32_t);
+};
+#define RS_VERIFY(K, MG) {K, MG, "verify_K" #K "_MG" #MG "_B256", rs_verify_kernel<K, MG, kBlock, true>}
+const VerifyVariant kVerify[] = {
+    RS_VERIFY(10, 4), RS_VERIFY(4, 4), RS_VERIFY(8, 6), RS_VERIFY(64, 16), RS_VERIFY(0, 4), RS_VERIFY(0, 8),
+};
+#undef RS_VERIFY
+
+const VerifyVariant& pick_verify(int k, int rows) {
+    for (const VerifyVariant& v : kVerify)
+        if (v.K != 0 && v.K == k && (rows <= v.MG || k == 64)) return v;  // RS(64, m > 16): row groups of 16
+    return kVerify[rows <= 4 ? 4 : 5];
+}
+
 }  // namespace
 
 const char* variant_name(int k, int rows) { return pick(k, rows).name; }
+
+const char* verify_variant_name(int k, int rows) { return pick_verify(k, rows).name; }
 
 bool mailbox_supported(int k, int rows) { return mailbox_variant(k, rows) != nullptr; }
 
@@ -568,6 +666,34 @@ hipError_t launch_matmul(MatArgs a, int max_e, hipStream_t stream) {
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     if (a.xcd == ~0u) a.xcd = a.chunks * a.groups;  // a stripe per XCD region
     hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(v.BT), lds, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify(MatArgs a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
+    if (a.stripes == 0 || a.ncols16 == 0 || a.m == 0) return hipSuccess;
+    const VerifyVariant& v = pick_verify(static_cast<int>(a.k), static_cast<int>(a.m));
+    const uint32_t total_it = (a.ncols16 + kBlock - 1) / kBlock;
+    static const uint32_t iters_cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    a.iters = std::min<uint32_t>(iters_cap, total_it);
+    a.chunks = (total_it + a.iters - 1) / a.iters;
+    a.groups = (a.m + v.MG - 1) / v.MG;
+    const size_t lds = static_cast<size_t>(a.k) * ((v.MG + 3) / 4) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = a.stripes * a.chunks * a.groups;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (a.xcd == ~0u) a.xcd = a.chunks * a.groups;
+    hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a, first_bad, shard_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_columns(const MatArgs& a, const uint2* pairs, uint32_t count, uint8_t* out,
+                                 hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_columns_kernel, dim3(count), dim3(64), 0, stream, a.data, a.parity, a.data_ss,
+                       a.parity_ss, a.pitch, a.k, a.k + a.m, pairs, out);
     return hipGetLastError();
 }
 

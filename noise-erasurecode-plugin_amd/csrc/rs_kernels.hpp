@@ -109,6 +109,21 @@ hipError_t launch_mailbox(MailboxHost* h, MailboxDev* d, const MailboxJobs& jobs
 // Which compiled variant serves (k, m): "K10_MG4" etc. (diagnostics).
 const char* variant_name(int k, int rows);  // kernel coding up to `rows` outputs per stripe
 
+// Verify twin of the encode launch (a: the encode pattern, all m rows of
+// every stripe, optionally a stripe list {stripe index, 0 << 8 | m}): the
+// kernel recomputes each stripe's parity and compares it with the stored
+// parity in registers.  first_bad[stripe] (device, preset to 0xFF bytes on
+// `stream` by the caller) receives by atomicMin the lowest byte offset below
+// shard_len at which a stored parity shard differs; parity is only read.
+hipError_t launch_verify(MatArgs a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream);
+const char* verify_variant_name(int k, int rows);  // "verify_K10_MG4_B256" etc.
+
+// Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
+// offset} (device, offset < shard_len) out[i * n + id] = that byte of shard
+// id, for every shard of the stripe (a: strided layout, k, m).
+hipError_t launch_gather_columns(const MatArgs& a, const uint2* pairs, uint32_t count, uint8_t* out,
+                                 hipStream_t stream);
+
 // Device-side copy of `count` pieces of `bytes` bytes (a multiple of 16):
 // piece i copies src + pieces[2i] to dst + pieces[2i+1] (16-byte aligned
 // offsets).  rs_decode_batch packs survivors / unpacks regenerated shards

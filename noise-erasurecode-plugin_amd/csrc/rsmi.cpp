@@ -36,6 +36,7 @@
 #include "pattern_index.hpp"
 #include "pinned.hpp"
 #include "rs_kernels.hpp"
+#include "scrub.hpp"
 
 namespace {
 
@@ -224,6 +225,7 @@ struct Lease {
     Staging st_onepat;                 // host-API decode: the one-pattern table, read in place by the kernel
     Staging st_out;                    // decode_in_place: regenerated shares when dst is not engine-pinned
     Staging st_in;                     // decode_staged / encode_staged: a small message's survivors
+    Staging st_scrub;                  // rs_correct_stripes: verdicts, stripe list, gathered columns
     // Mailbox grid of a staged single message (MailboxCall): the job board
     // in pinned coherent memory, its device alias and the grid's device
     // words; allocated on first use.
@@ -231,7 +233,7 @@ struct Lease {
     rsmi::MailboxHost* mb_dev = nullptr;
     rsmi::MailboxDev* mbd = nullptr;
     uint64_t mb_timeout = 0;  // the grid's wait for a post in device wall-clock ticks (mailbox_timeout_us)
-    DevBuf d_stripe_pat, d_batch, d_pack, d_pieces, d_onepat;
+    DevBuf d_stripe_pat, d_batch, d_pack, d_pieces, d_onepat, d_scrub;
     std::unique_ptr<rsmi::HostPipeline> pipe;  // host-buffer API, created on first use
     std::vector<uint32_t> pid, start;          // reconstruct scratch
     std::vector<uint64_t> sort_a, sort_b;      // (bucket, stripe) radix-sort scratch
@@ -294,7 +296,8 @@ struct Lease {
         st_onepat.destroy();
         st_out.destroy();
         st_in.destroy();
-        for (DevBuf* b : {&d_stripe_pat, &d_batch, &d_pack, &d_pieces, &d_onepat}) b->release();
+        st_scrub.destroy();
+        for (DevBuf* b : {&d_stripe_pat, &d_batch, &d_pack, &d_pieces, &d_onepat, &d_scrub}) b->release();
         if (mb) (void)hipHostFree(mb);
         if (mbd) (void)hipFree(mbd);
         for (hipEvent_t e : ev)
@@ -1043,6 +1046,126 @@ int reconstruct_host_table(rs_ctx* c, const uint64_t* tab, size_t len, size_t st
                                static_cast<const uint64_t*>(L.d_pieces.p), s);
     L.end(s);  // also when nothing was launched: the table copy wrote d_pieces on s
     return rc;
+}
+
+// ---------------------------------------------------------------- scrub ----
+// Verify launch on stream s: first_bad[0 .. stripes) is preset to
+// RS_VERIFY_CLEAN, then the verify twin of the split-table encode kernel
+// checks every stripe (desc == nullptr) or the `count` stripes listed in desc
+// (device, {stripe index, 0 << 8 | m}).
+int launch_verify_stripes(const rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                          size_t len, size_t stripes, const uint2* desc, size_t count, uint32_t* first_bad,
+                          hipStream_t s) {
+    if (hipMemsetAsync(first_bad, 0xFF, stripes * sizeof(uint32_t), s) != hipSuccess) return RS_EDEVICE;
+    if (c->m == 0 || count == 0) return RS_OK;
+    rsmi::MatArgs a = base_args(c, const_cast<void*>(data), dss, const_cast<void*>(parity), pss, pitch, len, count);
+    set_patterns(c, 1, c->d_encpat.p, a);
+    a.stripe_desc = desc;
+    a.xcd = c->xcd_split_enc;
+    return hip_status(rsmi::launch_verify(a, first_bad, static_cast<uint32_t>(len), s));
+}
+
+// rs_correct_stripes on stream s with lease L.  Device workspace (L.d_scrub)
+// and its pinned mirror (L.st_scrub), all O(stripes):
+//   first_bad u32 [stripes] | list uint2 [stripes] | columns u8 [stripes * n]
+// `list` holds the gather's {stripe, byte offset} pairs, then the re-verify's
+// {stripe, m} descriptors of the same live stripes.
+int correct_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                    size_t stripes, int* status, uint8_t* rewritten, hipStream_t s) {
+    const size_t n = static_cast<size_t>(c->n);
+    const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
+    const size_t cols_off = list_off + stripes * sizeof(uint2);
+    const size_t bytes = cols_off + stripes * n;
+    L.begin(s);
+    if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_scrub.p);
+    uint8_t* const db = static_cast<uint8_t*>(L.d_scrub.p);
+    uint32_t* const h_fb = reinterpret_cast<uint32_t*>(hb);
+    uint2* const h_list = reinterpret_cast<uint2*>(hb + list_off);
+    uint8_t* const h_cols = hb + cols_off;
+    uint32_t* const d_fb = reinterpret_cast<uint32_t*>(db);
+    uint2* const d_list = reinterpret_cast<uint2*>(db + list_off);
+    uint8_t* const d_cols = db + cols_off;
+    // Every exit records the lease's last device use.
+    struct End {
+        Lease& L;
+        hipStream_t s;
+        ~End() { L.end(s); }
+    } end_guard{L, s};
+
+    // Verdicts of the stripes verified last (all, or the live list) to the host.
+    auto fetch_verdicts = [&]() -> int {
+        if (hipMemcpyAsync(h_fb, d_fb, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return RS_EDEVICE;
+        return RS_OK;
+    };
+    int rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, d_fb, s);
+    if (rc == RS_OK) rc = fetch_verdicts();
+    if (rc != RS_OK) return rc;
+    std::vector<uint32_t> live;
+    for (size_t i = 0; i < stripes; ++i)
+        if (h_fb[i] != RS_VERIFY_CLEAN) live.push_back(static_cast<uint32_t>(i));
+    if (live.empty()) return RS_OK;
+
+    // known: every shard located so far (the set L of the stripe; reported
+    // through `rewritten`); erased: the same for the live stripes only, what
+    // each round's reconstruct regenerates.
+    std::vector<uint8_t> known(stripes * n, 0), erased(stripes * n, 0);
+    bool failed = false;
+    auto give_up = [&](uint32_t i) {
+        if (status) status[i] = RS_ETOO_MANY_ERRORS;
+        std::fill_n(erased.begin() + static_cast<size_t>(i) * n, n, uint8_t(0));
+        failed = true;
+    };
+    const rsmi::MatArgs ga = base_args(c, data, dss, parity, pss, pitch, len, stripes);
+    for (int round = 0; round < c->m && !live.empty(); ++round) {
+        // The column at each live stripe's first inconsistent offset.
+        for (size_t j = 0; j < live.size(); ++j) {
+            if (h_fb[live[j]] >= len) return RS_EDEVICE;  // never: verify reports offsets below shard_len
+            h_list[j] = make_uint2(live[j], h_fb[live[j]]);
+        }
+        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess ||
+            rsmi::launch_gather_columns(ga, d_list, static_cast<uint32_t>(live.size()), d_cols, s) != hipSuccess ||
+            hipMemcpyAsync(h_cols, d_cols, live.size() * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return RS_EDEVICE;
+        size_t kept = 0;
+        for (size_t j = 0; j < live.size(); ++j) {
+            const uint32_t i = live[j];
+            uint8_t* kn = &known[static_cast<size_t>(i) * n];
+            // An inconsistent column always holds a wrong share outside the
+            // set, so a round that locates none is a failure too.
+            if (rsmi::scrub_locate(c->k, c->n, kn, h_cols + j * n) <= 0) {
+                give_up(i);
+                continue;
+            }
+            std::copy(kn, kn + n, erased.begin() + static_cast<size_t>(i) * n);
+            live[kept++] = i;
+        }
+        live.resize(kept);
+        if (live.empty()) break;
+        // All of every live stripe's set, in one batched reconstruct.
+        rc = reconstruct(c, L, data, dss, parity, pss, pitch, len, stripes, erased.data(), nullptr, s);
+        if (rc != RS_OK) return rc;
+        if (rewritten)
+            for (uint32_t i : live) std::copy_n(&known[static_cast<size_t>(i) * n], n, rewritten + static_cast<size_t>(i) * n);
+        // Verify the live stripes again, through the stripe list.
+        for (size_t j = 0; j < live.size(); ++j) h_list[j] = make_uint2(live[j], static_cast<uint32_t>(c->m));
+        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
+            return RS_EDEVICE;
+        rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, d_list, live.size(), d_fb, s);
+        if (rc == RS_OK) rc = fetch_verdicts();
+        if (rc != RS_OK) return rc;
+        kept = 0;
+        for (uint32_t i : live) {
+            if (h_fb[i] == RS_VERIFY_CLEAN) std::fill_n(erased.begin() + static_cast<size_t>(i) * n, n, uint8_t(0));
+            else live[kept++] = i;
+        }
+        live.resize(kept);
+    }
+    for (uint32_t i : live) give_up(i);  // still inconsistent after m rounds
+    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
 }
 
 // Holds the least busy member of a device set for one call.
@@ -2329,6 +2452,7 @@ int rs_encode_matrix(const rs_ctx* c, uint8_t* out) {
 const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (!c) return "";
     if (c->set) return rs_kernel_name(rsmi::set_member(c->set, 0), which);
+    if (which == 2) return rsmi::verify_variant_name(c->k, c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2503,6 +2627,45 @@ int rs_reconstruct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size
     if (!lg.L) return RS_ENOMEM;
     return reconstruct(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, erased, nullptr,
                        static_cast<hipStream_t>(stream));
+}
+
+int rs_verify_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                      size_t len, size_t stripes, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->set) {
+        rs_ctx* mc = routed(c, c->m > 0 ? data : first_bad);
+        return mc ? rs_verify_stripes(mc, data, dss, parity, pss, pitch, len, stripes, first_bad, stream) : RS_EINVAL;
+    }
+    // Reads only state that is immutable after rs_new: no lock, no lease.
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    return launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, first_bad,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                       size_t stripes, int* status, uint8_t* rewritten, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->m > 0 && stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (c->set && c->m > 0) {
+        rs_ctx* mc = routed(c, data);
+        return mc ? rs_correct_stripes(mc, data, dss, parity, pss, pitch, len, stripes, status, rewritten, stream)
+                  : RS_EINVAL;
+    }
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (rewritten) std::memset(rewritten, 0, stripes * static_cast<size_t>(c->n));
+    if (c->m == 0) return RS_OK;  // no parity: every stripe is a codeword
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return correct_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, status, rewritten,
+                           static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

@@ -31,12 +31,14 @@ RS_EINVAL = -8
 RS_EDEVICE = -9
 RS_ENOMEM = -10
 RS_ETOO_MANY_ERRORS = -16
+RS_VERIFY_CLEAN = 0xFFFFFFFF  # rs_verify_stripes: the stripe is a codeword
 
 # Every symbol include/rsmi.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = (
     "rs_new", "rs_new_on_device", "rs_free", "rs_k", "rs_n", "rs_device",
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
+    "rs_verify_stripes", "rs_correct_stripes",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -101,6 +103,8 @@ def _lib() -> ctypes.CDLL:
             "rs_encode_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp]),
             "rs_reconstruct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_reconstruct_ptrs": (i32, [vp, vp, sz, sz, vp, vp]),
+            "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
+            "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
             "rs_prepare_patterns": (i32, [vp, i32, vp]),
@@ -392,6 +396,32 @@ class FEC:
                                              parity_stride, pitch, shard_len, stripes,
                                              ctypes.cast(buf, ctypes.c_void_p), stream or None),
                "rs_reconstruct_stripes")
+
+    def verify_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                       pitch: int, shard_len: int, stripes: int, first_bad_ptr: int,
+                       stream: int = 0) -> None:
+        """rs_verify_stripes: first_bad_ptr is a device array of `stripes`
+        uint32; entry s receives the lowest byte offset at which stripe s's
+        stored parity differs from the recomputed one, or RS_VERIFY_CLEAN.
+        Enqueued on stream."""
+        _check(_lib().rs_verify_stripes(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                        pitch, shard_len, stripes, first_bad_ptr or None,
+                                        stream or None), "rs_verify_stripes")
+
+    def correct_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                        pitch: int, shard_len: int, stripes: int, stream: int = 0):
+        """rs_correct_stripes (scrub): (status, rewritten) -- status[s] is
+        RS_OK or RS_ETOO_MANY_ERRORS, rewritten[s * n + i] is non-zero where
+        shard i of stripe s was regenerated.  Raises only for argument,
+        device or memory errors."""
+        st = (ctypes.c_int * max(stripes, 1))()
+        rw = ctypes.create_string_buffer(max(stripes * self.n, 1))
+        rc = _lib().rs_correct_stripes(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                       pitch, shard_len, stripes, st,
+                                       ctypes.cast(rw, ctypes.c_void_p), stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_stripes")
+        return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
 
     def reconstruct_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
                          stream: int = 0) -> None:
