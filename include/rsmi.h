@@ -72,9 +72,9 @@ int rs_device(const rs_ctx *ctx);
 int rs_encode_matrix(const rs_ctx *ctx, uint8_t *out);
 const char *rs_strerror(int status);
 /* Diagnostics: name of the kernel that serves encode (which = 0),
- * reconstruct (which = 1) or verify (which = 2) for this ctx, e.g.
- * "bitslice_k64_m16", "K10_MG4_B256" or "verify_K10_MG4_B256" (no reference
- * counterpart). */
+ * reconstruct (which = 1), verify (which = 2) or update (which = 3) for this
+ * ctx, e.g. "bitslice_k64_m16", "K10_MG4_B256", "verify_K10_MG4_B256" or
+ * "update_MG4_B256" (no reference counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -195,6 +195,44 @@ int rs_correct_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void 
                        size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
                        size_t stripes, int *status, uint8_t *rewritten, void *stream);
 
+/* In-place parity update: overwrite data shards of stripes that already hold
+ * parity and patch that parity from the difference alone.  Layout and
+ * alignment rules as rs_encode_stripes.
+ * updates: HOST array of `count` entries, not retained.  For each entry, data
+ * shard `shard` of stripe `stripe` takes the contents at src (DEVICE, 16-byte
+ * aligned, round_up(shard_len, 16) readable bytes, all of which are coded and
+ * committed), and every parity shard r of that stripe becomes
+ *     parity[r] ^= E[k + r][shard] * (old ^ new)
+ * with E the encode matrix (rs_encode_matrix).  The stored parity is TRUSTED:
+ * it is patched, not recomputed, so a stripe that was a codeword before the
+ * call is one after it, and a stripe that was not (rs_verify_stripes) stays
+ * inconsistent by the same difference.  Stripes and shards not listed are
+ * neither read nor written; the other k - 1 data shards of an updated stripe
+ * need not even be present.  Per stripe with j changed shards the call moves
+ * (3j + 2m) * S bytes where copying the shards in and rs_encode_stripes moves
+ * (2j + k + m) * S: it pays off while j + m < k, and the caller chooses.
+ * A slice update -- bytes [o, o + l) of the shards, o a multiple of 16 -- is
+ * the same call with data and parity advanced by o and shard_len = l (src then
+ * holds the slice's new bytes); pitch and strides stay.
+ * All or nothing: RS_EINVAL for NULL updates, stripe >= stripes, the same
+ * (stripe, shard) listed twice, a NULL or misaligned src, a src range that
+ * intersects the extent of the call's data or parity region, reserved != 0,
+ * or more than 2^31 - 1 blocks; RS_EBAD_SHARE_ID for shard >= k; nothing is
+ * launched then.  count == 0, stripes == 0 or shard_len == 0: RS_OK, nothing
+ * launched.  With m == 0 only the data shards are overwritten.
+ * Enqueued on stream; returns when queued (the small job tables are staged
+ * through pinned memory). */
+typedef struct rs_shard_update {
+    uint64_t stripe;    /* < stripes */
+    uint32_t shard;     /* data shard id, < k */
+    uint32_t reserved;  /* 0 */
+    const void *src;    /* DEVICE, 16-byte aligned, round_up(shard_len, 16) readable bytes */
+} rs_shard_update;
+int rs_update_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                      size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                      size_t stripes, const rs_shard_update *updates, size_t count,
+                      void *stream);
+
 /* rs_reconstruct_ptrs: rs_reconstruct_stripes with shards anywhere in
  * device memory.  shard_ptrs is a DEVICE array [stripes][n] of device
  * addresses (16-byte aligned): shard i of stripe s is read (survivor) or
@@ -229,6 +267,8 @@ enum {
     RS_STAT_ENCODE_BATCHES = 9,    /* rs_encode_batch GPU passes (one per staging group) */
     RS_STAT_MAILBOX_CALLS = 10,    /* rs_encode / rs_decode calls whose chunks went to a mailbox grid */
     RS_STAT_MAILBOX_RECOVERED = 11, /* ... of them with a chunk the grid left undone (launched by the caller) */
+    RS_STAT_UPDATE_STRIPES = 12,   /* stripes patched by rs_update_stripes             */
+    RS_STAT_UPDATE_COPY_COMMITS = 13, /* rs_update_stripes calls whose data commit ran as a separate copy pass */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -331,7 +371,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    contiguous ranges (rs_partition), each range on its member's thread, all
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
- *    rs_verify_stripes, rs_correct_stripes,
+ *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes,
  *    rs_reconstruct_ptrs, rs_fill_splitmix, rs_blake2b_device) run on a
  *    member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs

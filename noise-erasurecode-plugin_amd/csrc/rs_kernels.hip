@@ -427,6 +427,146 @@ __global__ __launch_bounds__(64) void gather_columns_kernel(const uint8_t* data,
     }
 }
 
+// In-place parity update (rs_kernels.hpp UpdArgs): matmul_block's block
+// decomposition with the job's j changed shards as the runtime "k".  The
+// accumulators start as the stored parity columns (as in the verify twin),
+// the inputs are old ^ new, the coefficients single columns of the encode
+// matrix, and the accumulators go back to the addresses they came from.
+// LDS: [j][MG/4][20] table dwords | j old-shard pointers | j new-shard pointers.
+template <int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG % 4 == 0, "whole sub-steps");
+    constexpr int TG = MG / kRowsPerStep;  // sub-steps per changed shard
+    // Changed shards whose old/new loads are in flight, next to the MG parity
+    // loads.  2, not matmul_block's 8: the common update changes one shard
+    // of a stripe, and 4 cost 138 / 129 / 244 VGPRs (MG 4 / 8 / 16) against
+    // 104 / 106 / 198.
+    constexpr int JB = 2;
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const UpdateJob job = a.jobs[b / a.chunks];
+    const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe))) |
+                       (static_cast<uint64_t>(static_cast<uint32_t>(
+                            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe >> 32))))
+                        << 32);
+    const UpdateEntry* ent = a.entries + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.first));
+    const int j = __builtin_amdgcn_readfirstlane(job.j);
+    const int row0 = static_cast<int>(grp) * MG;
+    const int eg = min(MG, static_cast<int>(a.m) - row0);  // >= 1: groups = ceil(m / MG)
+
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** optr = reinterpret_cast<uint8_t**>(tw + j * TG * kStepWords);
+    uint8_t** nptr = optr + j;
+    uint8_t* dbase = a.data + s * a.data_ss;
+    for (int i = threadIdx.x; i < j; i += BT) {
+        const UpdateEntry e = ent[i];
+        optr[i] = dbase + static_cast<uint64_t>(e.shard) * a.pitch;
+        nptr[i] = reinterpret_cast<uint8_t*>(e.src);
+    }
+    // Parity rows of this group; rows past eg are never dereferenced.
+    uint8_t* pp[MG];
+#pragma unroll
+    for (int r = 0; r < MG; ++r)
+        pp[r] = uniform_ptr(a.parity + s * a.parity_ss + static_cast<uint64_t>(row0 + r) * a.pitch);
+
+    const uint32_t last = a.ncols16 - 1;
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    uint32_t acc[TG][kRowsPerStep][4];
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                uint4 p = make_uint4(0u, 0u, 0u, 0u);
+                if (g * kRowsPerStep + r < eg) p = gload16<NT>(pp[g * kRowsPerStep + r] + at);
+                acc[g][r][0] = p.x;
+                acc[g][r][1] = p.y;
+                acc[g][r][2] = p.z;
+                acc[g][r][3] = p.w;
+            }
+    };
+    // The first iteration's loads -- the stored parity columns and the old
+    // and new columns of the first JB changed shards, their addresses taken
+    // straight from the entry table -- go out before the table build; with
+    // one iteration per block and j <= JB that is the whole data path.
+    load_stored(off0);
+    uint4 xo[JB], xn[JB];
+#pragma unroll
+    for (int q = 0; q < JB; ++q) {
+        if (q >= j) break;
+        const UpdateEntry e = ent[q];
+        const uint32_t sh = __builtin_amdgcn_readfirstlane(e.shard);
+        xo[q] = gload16<NT>(uniform_ptr(dbase + static_cast<uint64_t>(sh) * a.pitch) + off0);
+        xn[q] = gload16<NT>(uniform_ptr(reinterpret_cast<uint8_t*>(e.src)) + off0);
+    }
+    // Split tables: sub-step (c, g) holds E[k + row0 + 4g .. + 3][shard_c].
+    for (int idx = threadIdx.x; idx < j * MG; idx += BT) {
+        const int c = idx / MG, t = idx - c * MG;
+        const uint32_t cf = (t < eg) ? a.enc[static_cast<size_t>(a.k + row0 + t) * a.k + ent[c].shard] : 0u;
+        build_tables(cf, &tw[(c * TG + t / kRowsPerStep) * kStepWords + (t % kRowsPerStep) * 5]);
+    }
+    __syncthreads();
+
+    const int tg_used = (eg + kRowsPerStep - 1) / kRowsPerStep;
+    bool preloaded = true;
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;
+        // Tail lanes re-read the last column and store nothing: the lane that
+        // owns that column may have patched it already.
+        const uint32_t off = (ok ? col : last) * 16u;
+        if (!preloaded) load_stored(off);
+        for (int jb = 0; jb < j; jb += JB) {
+            if (!preloaded) {
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (jb + q >= j) break;
+                    xo[q] = gload16<NT>(uniform_ptr(optr[jb + q]) + off);
+                    xn[q] = gload16<NT>(uniform_ptr(nptr[jb + q]) + off);
+                }
+            }
+            preloaded = false;
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb * TG) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (jb + q >= j) break;
+                const uint4 x = make_uint4(xo[q].x ^ xn[q].x, xo[q].y ^ xn[q].y, xo[q].z ^ xn[q].z, xo[q].w ^ xn[q].w);
+#pragma unroll
+                for (int g = 0; g < TG; ++g) {
+                    const int step = (jb + q) * TG + g;
+                    const bool more = (g + 1 < TG) || (q + 1 < JB && jb + q + 1 < j);
+                    if (more) load_step(lds4 + static_cast<size_t>(step + 1) * (kStepWords / 4), TB);
+                    if (TG == 1 || g < tg_used) mac_step(acc[g], x, TA);
+                    step_fence(acc[g]);
+#pragma unroll
+                    for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+                }
+                // Commit: the only block that reads this shard's old column
+                // has consumed it.
+                if (a.commit && ok) gstore16<NT>(uniform_ptr(optr[jb + q]) + off, xn[q]);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                const int t = g * kRowsPerStep + r;
+                if (t >= eg) break;
+                if (ok) gstore16<NT>(pp[t] + off, make_uint4(acc[g][r][0], acc[g][r][1], acc[g][r][2], acc[g][r][3]));
+            }
+    }
+}
+
 template <int K, int MG, int BT, bool NT>
 __global__ __launch_bounds__(BT) void rs_matmul_kernel(MatArgs a) {
     extern __shared__ uint4 lds4[];
@@ -614,7 +754,63 @@ const VerifyVariant& pick_verify(int k, int rows) {
     return kVerify[rows <= 4 ? 4 : 5];
 }
 
+// Update variants: the smallest row group that holds all m rows commits the
+// data in-kernel; m > 16 goes through row groups of 16.
+struct UpdateVariant {
+    int MG;
+    const char* name;
+    void (*fn)(UpdArgs);
+};
+#define RS_UPDATE(MG) {MG, "update_MG" #MG "_B256", rs_update_kernel<MG, kBlock, true>}
+const UpdateVariant kUpdate[] = {RS_UPDATE(4), RS_UPDATE(8), RS_UPDATE(16)};
+#undef RS_UPDATE
+
+constexpr size_t kUpdateLdsMax = 64 * 1024;
+size_t update_lds(int mg, uint32_t max_j) {
+    return static_cast<size_t>(max_j) * (mg / kRowsPerStep) * kStepWords * 4 + 2 * static_cast<size_t>(max_j) * sizeof(void*);
+}
+
+// max_j = 0: the variant named for m.  A job of more than 195 shards does not
+// fit the LDS with row groups of 16; it takes row groups of 8.
+const UpdateVariant& pick_update(int m, uint32_t max_j) {
+    const UpdateVariant& v = kUpdate[m <= 4 ? 0 : m <= 8 ? 1 : 2];
+    return update_lds(v.MG, max_j) <= kUpdateLdsMax ? v : kUpdate[1];
+}
+
 }  // namespace
+
+const char* update_variant_name(int m) { return pick_update(m, 0).name; }
+
+bool plan_update(UpdArgs* a, uint32_t max_j) {
+    const UpdateVariant& v = pick_update(static_cast<int>(a->m), max_j);
+    const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
+    static const uint32_t iters_cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    a->iters = std::min<uint32_t>(iters_cap, std::max<uint32_t>(total_it, 1));
+    a->chunks = (total_it + a->iters - 1) / a->iters;
+    a->mg = static_cast<uint32_t>(v.MG);
+    a->groups = (a->m + a->mg - 1) / a->mg;
+    a->commit = a->groups == 1;
+    const uint64_t blocks = static_cast<uint64_t>(a->njobs) * a->chunks * a->groups;
+    if (blocks > 0x7FFFFFFFull) return false;
+    if (a->xcd == ~0u) a->xcd = a->chunks * a->groups;  // a stripe per XCD region
+    return true;
+}
+
+hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.m == 0 || max_j == 0) return hipSuccess;
+    const UpdateVariant* v = nullptr;
+    for (const UpdateVariant& u : kUpdate)
+        if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
+    const size_t lds = update_lds(static_cast<int>(a.mg), max_j);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
 
 const char* variant_name(int k, int rows) { return pick(k, rows).name; }
 

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "update_plan.hpp"
+
 namespace rsmi {
 
 // One launch codes many stripes.  For stripe s the kernel reads the k
@@ -117,6 +119,36 @@ const char* variant_name(int k, int rows);  // kernel coding up to `rows` output
 // shard_len at which a stored parity shard differs; parity is only read.
 hipError_t launch_verify(MatArgs a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream);
 const char* verify_variant_name(int k, int rows);  // "verify_K10_MG4_B256" etc.
+
+// In-place parity update (rs_update_stripes): job b = {stripe, first, j} of
+// `jobs` overwrites data shards entries[first .. first + j) of its stripe with
+// the contents at their src and patches every parity row r of the stripe,
+//     parity[r] ^= enc[(k + r) * k + shard_c] * (old_c ^ new_c).
+// A block is {job, 4 KiB column chunk, row group of MG parity rows}.
+struct UpdArgs {
+    uint8_t* data;
+    uint8_t* parity;
+    uint64_t data_ss, parity_ss, pitch;  // strided layout, as MatArgs
+    uint32_t ncols16;                    // 16-byte columns per shard
+    uint32_t k, m;
+    const uint8_t* enc;          // [k + m][k] encode matrix (device)
+    const UpdateJob* jobs;       // [njobs] (device), at most one per stripe
+    const UpdateEntry* entries;  // (device)
+    uint32_t njobs;
+    uint32_t xcd;                // XCD-aware block order, as MatArgs
+    // Filled in by plan_update:
+    uint32_t chunks, groups, iters;
+    uint32_t mg;      // row-group size of the variant chosen
+    uint32_t commit;  // 1: one row group covers all m rows and the block stores the new
+                      // contents over the old itself; 0 (several row groups, each reading
+                      // the old data): the kernel leaves the data alone and the caller
+                      // copies it in behind the kernel
+};
+// Chooses the variant for (a->m, max_j = the largest j of any job) and fills
+// in the launch plan; false when the grid would exceed 2^31 - 1 blocks.
+bool plan_update(UpdArgs* a, uint32_t max_j);
+hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream);  // a: planned
+const char* update_variant_name(int m);  // "update_MG4_B256" etc.
 
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard

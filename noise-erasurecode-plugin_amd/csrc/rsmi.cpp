@@ -37,6 +37,7 @@
 #include "pinned.hpp"
 #include "rs_kernels.hpp"
 #include "scrub.hpp"
+#include "update_plan.hpp"
 
 namespace {
 
@@ -362,6 +363,8 @@ struct rs_ctx {
     std::atomic<int64_t> rec_stripes_table{0}, rec_stripes_syndrome{0};  // launch_reconstruct's kernels (rs_stat)
     std::atomic<int64_t> encode_batches{0};                              // rs_encode_batch calls through the GPU
     std::atomic<int64_t> mailbox_calls{0}, mailbox_recovered{0};         // MailboxCall (rs_stat)
+    std::atomic<int64_t> update_stripes{0}, update_copy_commits{0};      // rs_update_stripes (rs_stat)
+    uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
     hipEvent_t caller_ev = nullptr;      // the building caller's stream tail (build_after_caller)
@@ -1166,6 +1169,70 @@ int correct_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, s
     }
     for (uint32_t i : live) give_up(i);  // still inconsistent after m rounds
     return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+}
+
+// --------------------------------------------------------------- update ----
+// rs_update_stripes on stream s with lease L: the planned job and entry
+// tables (and, for the copy commit, the {src, dst} address pairs) go through
+// the lease's pinned staging into its device buffer in one upload, as
+// launch_reconstruct's descriptors do; then the update kernel, then -- when
+// the kernel could not commit the data itself -- the copy of the new shards
+// into place, on the same stream behind it.
+int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                   const rsmi::UpdatePlan& plan, hipStream_t s) {
+    const size_t njobs = plan.jobs.size(), count = plan.entries.size();
+    rsmi::UpdArgs a{};
+    a.data = static_cast<uint8_t*>(data);
+    a.parity = static_cast<uint8_t*>(parity);
+    a.data_ss = dss;
+    a.parity_ss = pss;
+    a.pitch = pitch;
+    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
+    a.k = static_cast<uint32_t>(c->k);
+    a.m = static_cast<uint32_t>(c->m);
+    a.enc = static_cast<const uint8_t*>(c->d_gf.p);
+    a.njobs = static_cast<uint32_t>(njobs);
+    a.xcd = c->xcd_update;
+    if (!rsmi::plan_update(&a, plan.max_j)) return RS_EINVAL;
+    const bool copy_commit = c->m == 0 || !a.commit;
+    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
+    if (copy_commit && count * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull) return RS_EINVAL;
+    const size_t ent_off = njobs * sizeof(rsmi::UpdateJob);
+    const size_t pieces_off = ent_off + count * sizeof(rsmi::UpdateEntry);
+    const size_t bytes = pieces_off + (copy_commit ? count * 2 * sizeof(uint64_t) : 0);
+    L.begin(s);  // the table buffer's previous readers
+    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+    std::memcpy(hb, plan.jobs.data(), ent_off);
+    std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::UpdateEntry));
+    if (copy_commit) {
+        uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
+        for (const rsmi::UpdateJob& job : plan.jobs)
+            for (uint32_t i = job.first; i < job.first + job.j; ++i) {
+                pieces[2 * i] = plan.entries[i].src;
+                pieces[2 * i + 1] = reinterpret_cast<uintptr_t>(data) + job.stripe * dss + plan.entries[i].shard * pitch;
+            }
+    }
+    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
+    L.st_stripe.release_after(s);
+    if (e != hipSuccess) {
+        L.end(s);
+        return RS_EDEVICE;
+    }
+    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    a.jobs = reinterpret_cast<const rsmi::UpdateJob*>(db);
+    a.entries = reinterpret_cast<const rsmi::UpdateEntry*>(db + ent_off);
+    if (c->m > 0) e = rsmi::launch_update(a, plan.max_j, s);
+    // The pieces hold absolute addresses: offsets from a null base.
+    if (e == hipSuccess && copy_commit)
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
+                                     static_cast<uint32_t>(count), round_up(len, 16), s);
+    L.end(s);
+    if (e == hipSuccess) {
+        c->update_stripes += static_cast<int64_t>(njobs);
+        if (copy_commit) ++c->update_copy_commits;
+    }
+    return hip_status(e);
 }
 
 // Holds the least busy member of a device set for one call.
@@ -2293,6 +2360,9 @@ int rs_new_on_device(int k, int n, int device, rs_ctx** out) {
         c->xcd_split_rec = c->xcd ? ~0u : 0u;
         const char* qv = std::getenv("RSMI_XCD_REC_REGION");  // A/B knob: blocks per XCD region
         if (qv) c->xcd_split_rec = static_cast<uint32_t>(std::min(std::max(0, std::atoi(qv)), 1 << 20));
+        c->xcd_update = c->xcd ? ~0u : 0u;
+        const char* uv = std::getenv("RSMI_XCD_UPD_REGION");  // A/B knob: blocks per XCD region
+        if (uv) c->xcd_update = static_cast<uint32_t>(std::min(std::max(0, std::atoi(uv)), 1 << 20));
         const char* bv = std::getenv("RSMI_XCD_BS_STRIPES");  // A/B knob: stripes per region (bit-sliced)
         if (bv && c->xcd) c->xcd = static_cast<uint32_t>(std::min(std::max(1, std::atoi(bv)), 64));
     }
@@ -2453,6 +2523,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (!c) return "";
     if (c->set) return rs_kernel_name(rsmi::set_member(c->set, 0), which);
     if (which == 2) return rsmi::verify_variant_name(c->k, c->m);
+    if (which == 3) return rsmi::update_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2503,6 +2574,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_ENCODE_BATCHES: return c->encode_batches.load();
         case RS_STAT_MAILBOX_CALLS: return c->mailbox_calls.load();
         case RS_STAT_MAILBOX_RECOVERED: return c->mailbox_recovered.load();
+        case RS_STAT_UPDATE_STRIPES: return c->update_stripes.load();
+        case RS_STAT_UPDATE_COPY_COMMITS: return c->update_copy_commits.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -2666,6 +2739,37 @@ int rs_correct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t p
     if (!lg.L) return RS_ENOMEM;
     return correct_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, status, rewritten,
                            static_cast<hipStream_t>(stream));
+}
+
+int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                      size_t stripes, const rs_shard_update* updates, size_t count, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!updates) return RS_EINVAL;
+    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->set) {
+        rs_ctx* mc = routed(c, data);
+        return mc ? rs_update_stripes(mc, data, dss, parity, pss, pitch, len, stripes, updates, count, stream)
+                  : RS_EINVAL;
+    }
+    rsmi::UpdatePlan plan;
+    const int rc = rsmi::plan_updates(c->k, stripes, updates, count, &plan);
+    if (rc != RS_OK) return rc;
+    // No src may lie in the call's data or parity region: a block would read
+    // as "new" what another block is overwriting.
+    const size_t span = round_up(len, 16);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
+    const uintptr_t d1 = d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span;
+    const uintptr_t p1 = c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0;
+    for (const rsmi::UpdateEntry& e : plan.entries) {
+        const uintptr_t s0 = static_cast<uintptr_t>(e.src), s1 = s0 + span;
+        if ((s0 < d1 && d0 < s1) || (s0 < p1 && p0 < s1)) return RS_EINVAL;
+    }
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return update_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

@@ -38,7 +38,7 @@ EXPORTS = (
     "rs_new", "rs_new_on_device", "rs_free", "rs_k", "rs_n", "rs_device",
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
-    "rs_verify_stripes", "rs_correct_stripes",
+    "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -57,6 +57,18 @@ class StripePart(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("data_stripe_stride", ctypes.c_size_t),
                 ("parity", ctypes.c_void_p), ("parity_stripe_stride", ctypes.c_size_t),
                 ("stripes", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
+
+
+class ShardUpdate(ctypes.Structure):
+    """rs_shard_update (include/rsmi.h): one changed data shard."""
+
+    _fields_ = [("stripe", ctypes.c_uint64), ("shard", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("src", ctypes.c_void_p)]
+
+
+def shard_updates(updates: Sequence[tuple]) -> ctypes.Array:
+    """The rs_shard_update table of (stripe, shard, src_ptr) tuples."""
+    return (ShardUpdate * len(updates))(*[ShardUpdate(s, i, 0, p) for s, i, p in updates])
 
 
 class RSError(Exception):
@@ -105,6 +117,7 @@ def _lib() -> ctypes.CDLL:
             "rs_reconstruct_ptrs": (i32, [vp, vp, sz, sz, vp, vp]),
             "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
+            "rs_update_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
             "rs_prepare_patterns": (i32, [vp, i32, vp]),
@@ -270,7 +283,8 @@ class FEC:
             pass
 
     def kernel_name(self, which: int = 0) -> str:
-        """Kernel serving encode (0) or reconstruct (1): diagnostics."""
+        """Kernel serving encode (0), reconstruct (1), verify (2) or update
+        (3): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -423,6 +437,19 @@ class FEC:
             _check(rc, "rs_correct_stripes")
         return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
 
+    def update_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                       pitch: int, shard_len: int, stripes: int, updates: Sequence[tuple],
+                       stream: int = 0) -> None:
+        """rs_update_stripes: updates is a sequence of (stripe, shard,
+        src_ptr); data shard `shard` of stripe `stripe` takes the contents at
+        the device address src_ptr and the stripe's stored parity is patched
+        in place from old ^ new.  A caller that repeats a large list passes
+        the table shard_updates() built from it instead.  Enqueued on stream."""
+        arr = updates if isinstance(updates, ctypes.Array) else shard_updates(updates)
+        _check(_lib().rs_update_stripes(self._h, data_ptr, data_stride, parity_ptr or None, parity_stride,
+                                        pitch, shard_len, stripes, arr, len(updates), stream or None),
+               "rs_update_stripes")
+
     def reconstruct_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
                          stream: int = 0) -> None:
         """rs_reconstruct_ptrs: shard i of stripe s at the device address in
@@ -441,7 +468,8 @@ class FEC:
 
     (STAT_PATTERNS, STAT_EVICTIONS, STAT_BATCHES_IN_PLACE, STAT_BATCHES_STAGED, STAT_LEASES,
      STAT_ENCODES_IN_PLACE, STAT_DECODES_IN_PLACE, STAT_REC_STRIPES_TABLE, STAT_REC_STRIPES_SYNDROME,
-     STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED) = range(12)
+     STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
+     STAT_UPDATE_COPY_COMMITS) = range(14)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
