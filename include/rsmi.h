@@ -72,9 +72,10 @@ int rs_device(const rs_ctx *ctx);
 int rs_encode_matrix(const rs_ctx *ctx, uint8_t *out);
 const char *rs_strerror(int status);
 /* Diagnostics: name of the kernel that serves encode (which = 0),
- * reconstruct (which = 1), verify (which = 2) or update (which = 3) for this
- * ctx, e.g. "bitslice_k64_m16", "K10_MG4_B256", "verify_K10_MG4_B256" or
- * "update_MG4_B256" (no reference counterpart). */
+ * reconstruct (which = 1), verify (which = 2), update (which = 3) or degraded
+ * read (which = 4) for this ctx, e.g. "bitslice_k64_m16", "K10_MG4_B256",
+ * "verify_K10_MG4_B256", "update_MG4_B256" or "read_K10_MG4_B256" (no
+ * reference counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -233,6 +234,52 @@ int rs_update_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *
                       size_t stripes, const rs_shard_update *updates, size_t count,
                       void *stream);
 
+/* Degraded read: fetch listed shards of stripes while some of their shards
+ * are missing, without repairing anything.  Layout and alignment rules as
+ * rs_encode_stripes; erased is a HOST array of stripes * n flags as for
+ * rs_reconstruct_stripes.
+ * reads: HOST array of `count` entries, not retained.  For each entry, dst
+ * receives the contents of shard `shard` (data or parity) of stripe `stripe`:
+ * a shard that is not erased is copied; an erased one is computed from the k
+ * survivors Rebuild chooses for the stripe's erasure set (data shares first,
+ * then the highest-numbered parity) with the decode row of the ctx's pattern
+ * cache that rs_reconstruct_stripes would use for it (row t of a pattern
+ * regenerates the t-th erased id in increasing order, rs_pattern_rows).
+ * round_up(shard_len, 16) bytes of dst are written; those past shard_len are
+ * unspecified.
+ * The data and parity regions are only read; the slots of erased shards are
+ * never dereferenced, for reading or writing; stripes that are not listed are
+ * not touched and their erased flags not examined.  Per stripe with j wanted
+ * missing shards the call moves (k + j) * S bytes and does j * k multiplies
+ * per column, where the repair of its e erasures moves (k + e) * S and does
+ * e * k; wide codes are read with the split-table kernel too, never through
+ * the syndrome network.
+ * A slice read -- bytes [o, o + l) of the shards, o a multiple of 16 -- is
+ * the same call with data and parity advanced by o and shard_len = l; pitch
+ * and strides stay.
+ * All or nothing: RS_EINVAL for NULL erased or reads, stripe >= stripes, the
+ * same (stripe, shard) listed twice, a NULL or misaligned dst, reserved != 0,
+ * a dst range that intersects the extent of the call's data or parity region
+ * or another dst range, or more than 2^31 - 1 blocks; RS_EBAD_SHARE_ID for
+ * shard >= n; RS_ENOT_ENOUGH for a listed stripe that wants an erased shard
+ * and has more than m erasures (defects of the list are reported first);
+ * nothing is launched and no dst is written then.  A listed stripe with more
+ * than m erasures that wants present shards only is served.  count == 0,
+ * stripes == 0 or shard_len == 0: RS_OK, nothing launched.  With k == n every
+ * entry is a copy.
+ * Enqueued on stream; returns when queued (the small job tables are staged
+ * through pinned memory). */
+typedef struct rs_shard_read {
+    uint64_t stripe;    /* < stripes */
+    uint32_t shard;     /* any shard id, < n (data or parity) */
+    uint32_t reserved;  /* 0 */
+    void *dst;          /* DEVICE, 16-byte aligned, round_up(shard_len, 16) writable bytes */
+} rs_shard_read;
+int rs_read_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride,
+                    const void *parity, size_t parity_stripe_stride, size_t shard_pitch,
+                    size_t shard_len, size_t stripes, const uint8_t *erased,
+                    const rs_shard_read *reads, size_t count, void *stream);
+
 /* rs_reconstruct_ptrs: rs_reconstruct_stripes with shards anywhere in
  * device memory.  shard_ptrs is a DEVICE array [stripes][n] of device
  * addresses (16-byte aligned): shard i of stripe s is read (survivor) or
@@ -269,6 +316,8 @@ enum {
     RS_STAT_MAILBOX_RECOVERED = 11, /* ... of them with a chunk the grid left undone (launched by the caller) */
     RS_STAT_UPDATE_STRIPES = 12,   /* stripes patched by rs_update_stripes             */
     RS_STAT_UPDATE_COPY_COMMITS = 13, /* rs_update_stripes calls whose data commit ran as a separate copy pass */
+    RS_STAT_READ_REGENERATED = 14, /* shards regenerated by rs_read_stripes            */
+    RS_STAT_READ_COPIED = 15,      /* shards rs_read_stripes served by copy            */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -371,7 +420,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    contiguous ranges (rs_partition), each range on its member's thread, all
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
- *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes,
+ *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
  *    rs_reconstruct_ptrs, rs_fill_splitmix, rs_blake2b_device) run on a
  *    member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs

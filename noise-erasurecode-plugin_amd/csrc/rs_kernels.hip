@@ -567,6 +567,157 @@ __global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
     }
 }
 
+// Degraded read (rs_kernels.hpp ReadArgs): the split-table matmul_block with
+// the rows and the outputs taken from the job's entry table instead of the
+// pattern.  Row t of the block's group is row entries[first + row0 + t].row of
+// the cached pattern -- the pattern's other rows are neither multiplied nor
+// stored -- and its columns go to entries[first + row0 + t].dst with the same
+// 16-byte stores.  The survivors come from the strided layout through the
+// pattern's src ids; nothing in the stripes is written.
+// One sub-step per survivor (MG = 4) and only the group's eg wanted rows are
+// multiplied (mac_step_rows) whatever K is: the common read wants one row.
+// LDS: [k][20] table dwords | k survivor pointers.
+template <int K, int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
+    constexpr bool kRegPtrs = K > 0 && K <= 16;           // survivor bases kept in SGPRs
+    constexpr int JB = (K == 0) ? 8 : (K <= 16 ? K : 8);  // survivor loads in flight
+    const int k = K ? K : static_cast<int>(a.k);
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * kStepWords);
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const uint64_t ji = b / a.chunks;
+    const ReadJob job = a.jobs[ji];
+    const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe))) |
+                       (static_cast<uint64_t>(static_cast<uint32_t>(
+                            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe >> 32))))
+                        << 32);
+    const int j = __builtin_amdgcn_readfirstlane(job.j);
+    const int row0 = static_cast<int>(grp) * MG;
+    if (row0 >= j) return;  // whole block: uniform
+    const int eg = min(MG, j - row0);
+    const ReadEntry* ent = a.entries + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.first)) + row0;
+    const uint32_t pat = __builtin_amdgcn_readfirstlane(a.pats[ji]);
+
+    // This lane's coefficient byte for the table build is requested first, so
+    // waiting for it later does not wait for the survivor loads behind it.
+    const uint8_t* coef = a.coef + static_cast<size_t>(pat) * a.m * k;
+    constexpr bool one_coef = (K > 0 && K * MG <= BT);
+    uint32_t cbyte = 0u;
+    if constexpr (one_coef) {
+        const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+        if (static_cast<int>(threadIdx.x) < k * MG && t < eg) cbyte = coef[static_cast<size_t>(ent[t].row) * k + c];
+    }
+
+    const uint32_t* srcid = a.src + static_cast<size_t>(pat) * k;
+    uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
+    uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
+    uint8_t* sp[kRegPtrs ? K : 1];
+    if constexpr (kRegPtrs) {
+        uint32_t ids[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
+                                                     : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+    } else {
+        for (int i = threadIdx.x; i < k; i += BT) {
+            const uint32_t id = srcid[i];
+            sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                               : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+        }
+    }
+    const uint32_t last = a.ncols16 - 1;
+    // Survivor loads of the block's first iteration go out before the table
+    // build, as in matmul_block.
+    uint4 xpre[kRegPtrs ? K : 1];
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    if constexpr (kRegPtrs) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + off0);
+    }
+    // Destinations of the group's wanted rows; rows past eg have none.
+    uint8_t* dp[MG];
+#pragma unroll
+    for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(ent[t].dst)) : nullptr;
+    // Split tables of the wanted rows: survivor c's sub-step holds 4 x 5 dwords.
+    if constexpr (one_coef) {
+        if (static_cast<int>(threadIdx.x) < k * MG) {
+            const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+            build_tables(cbyte, &tw[c * kStepWords + t * 5]);
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < k * MG; idx += BT) {
+            const int c = idx / MG, t = idx - c * MG;
+            const uint32_t cf = (t < eg) ? coef[static_cast<size_t>(ent[t].row) * k + c] : 0u;
+            build_tables(cf, &tw[c * kStepWords + t * 5]);
+        }
+    }
+    __syncthreads();
+
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;
+        // Tail lanes re-read the last column (always in bounds) and skip the store.
+        const uint32_t off = (ok ? col : last) * 16u;
+        uint32_t acc[kRowsPerStep][4];
+#pragma unroll
+        for (int r = 0; r < kRowsPerStep; ++r)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) acc[r][w] = 0u;
+
+        for (int jb = 0; jb < k; jb += JB) {
+            uint4 xb[kRegPtrs ? 1 : JB];
+            uint4* x = kRegPtrs ? xpre : xb;
+            if constexpr (!kRegPtrs) {
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (K == 0 && jb + q >= k) break;
+                    x[q] = gload16<NT>(uniform_ptr(sptr[jb + q]) + off);
+                }
+            }
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (K == 0 && jb + q >= k) break;
+                const bool more = q + 1 < JB && (K != 0 || jb + q + 1 < k);
+                if (more) load_step(lds4 + static_cast<size_t>(jb + q + 1) * (kStepWords / 4), TB);
+                mac_step_rows(acc, x[q], TA, eg);
+                step_fence(acc);
+#pragma unroll
+                for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+            }
+        }
+        if constexpr (kRegPtrs) {
+            // Software pipelining: the next iteration's survivor loads go out
+            // before this iteration's stores.
+            const uint32_t ncol = colbase + cstride + threadIdx.x;
+            if (it + 1 < a.iters && colbase + cstride < a.ncols16) {
+                const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
+#pragma unroll
+                for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + noff);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < kRowsPerStep; ++t) {
+            if (t >= eg) break;
+            if (ok) gstore16<NT>(dp[t] + off, make_uint4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]));
+        }
+    }
+}
+
 template <int K, int MG, int BT, bool NT>
 __global__ __launch_bounds__(BT) void rs_matmul_kernel(MatArgs a) {
     extern __shared__ uint4 lds4[];
@@ -777,9 +928,55 @@ const UpdateVariant& pick_update(int m, uint32_t max_j) {
     return update_lds(v.MG, max_j) <= kUpdateLdsMax ? v : kUpdate[1];
 }
 
+// Read variants: always the split-table kernel with row groups of 4 wanted
+// rows, also for the codes whose reconstruct runs the syndrome network.
+struct ReadVariant {
+    int K;
+    const char* name;
+    void (*fn)(ReadArgs);
+};
+#define RS_READ(K) {K, "read_K" #K "_MG4_B256", rs_read_kernel<K, 4, kBlock, true>}
+const ReadVariant kRead[] = {RS_READ(10), RS_READ(4), RS_READ(8), RS_READ(64), RS_READ(0)};
+#undef RS_READ
+constexpr int kReadMG = 4;
+
+const ReadVariant& pick_read(int k) {
+    for (const ReadVariant& v : kRead)
+        if (v.K == k) return v;
+    return kRead[sizeof(kRead) / sizeof(kRead[0]) - 1];  // runtime k
+}
+
 }  // namespace
 
 const char* update_variant_name(int m) { return pick_update(m, 0).name; }
+
+const char* read_variant_name(int k) { return pick_read(k).name; }
+
+bool plan_read(ReadArgs* a, uint32_t max_j) {
+    const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
+    static const uint32_t iters_cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    a->iters = std::min<uint32_t>(iters_cap, std::max<uint32_t>(total_it, 1));
+    a->chunks = (total_it + a->iters - 1) / a->iters;
+    a->groups = (max_j + kReadMG - 1) / kReadMG;
+    const uint64_t blocks = static_cast<uint64_t>(a->njobs) * a->chunks * a->groups;
+    if (blocks > 0x7FFFFFFFull) return false;
+    if (a->xcd == ~0u) a->xcd = a->chunks * a->groups;  // a job per XCD region
+    return true;
+}
+
+hipError_t launch_read(const ReadArgs& a, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    const ReadVariant& v = pick_read(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
 
 bool plan_update(UpdArgs* a, uint32_t max_j) {
     const UpdateVariant& v = pick_update(static_cast<int>(a->m), max_j);

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "read_plan.hpp"
 #include "update_plan.hpp"
 
 namespace rsmi {
@@ -149,6 +150,35 @@ struct UpdArgs {
 bool plan_update(UpdArgs* a, uint32_t max_j);
 hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream);  // a: planned
 const char* update_variant_name(int m);  // "update_MG4_B256" etc.
+
+// Degraded read (rs_read_stripes): job b = {stripe, first, j} of `jobs`, whose
+// stripe uses decode pattern pats[b] of the ctx's pattern cache, regenerates
+// the j wanted missing shards entries[first .. first + j) from the pattern's k
+// survivors (strided layout, src[pat]):
+//     *entries[first + t].dst = sum_c coef[(pat * m + entries[first + t].row) * k + c] * shard[src[pat * k + c]]
+// A block is {job, 4 KiB column chunk, row group of MG wanted rows}.  The
+// stripes are only read; rows of the pattern that nobody wants are not coded.
+struct ReadArgs {
+    const uint8_t* data;
+    const uint8_t* parity;
+    uint64_t data_ss, parity_ss, pitch;  // strided layout, as MatArgs
+    uint32_t ncols16;                    // 16-byte columns per shard
+    uint32_t k, m;
+    const uint8_t* coef;       // [npat][m][k] (the pattern cache, as MatArgs)
+    const uint32_t* src;       // [npat][k]
+    const ReadJob* jobs;       // [njobs] (device), at most one per stripe
+    const ReadEntry* entries;  // (device)
+    const uint32_t* pats;      // [njobs] (device) pattern id of each job's stripe
+    uint32_t njobs;
+    uint32_t xcd;              // XCD-aware block order, as MatArgs
+    // Filled in by plan_read:
+    uint32_t chunks, groups, iters;
+};
+// Fills in the launch plan for max_j = the largest j of any job; false when
+// the grid would exceed 2^31 - 1 blocks.
+bool plan_read(ReadArgs* a, uint32_t max_j);
+hipError_t launch_read(const ReadArgs& a, hipStream_t stream);  // a: planned
+const char* read_variant_name(int k);  // "read_K10_MG4_B256" etc.
 
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard

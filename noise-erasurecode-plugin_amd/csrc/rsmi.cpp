@@ -364,6 +364,7 @@ struct rs_ctx {
     std::atomic<int64_t> encode_batches{0};                              // rs_encode_batch calls through the GPU
     std::atomic<int64_t> mailbox_calls{0}, mailbox_recovered{0};         // MailboxCall (rs_stat)
     std::atomic<int64_t> update_stripes{0}, update_copy_commits{0};      // rs_update_stripes (rs_stat)
+    std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1233,6 +1234,99 @@ int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, si
         if (copy_commit) ++c->update_copy_commits;
     }
     return hip_status(e);
+}
+
+// --------------------------------------------------------- degraded read ----
+// Launches a planned rs_read_stripes on stream s.  With jobs, pat_mu is held
+// (shared or exclusive) and L.pid holds the built pattern of every job.  The
+// job and entry tables, the jobs' pattern ids and the {src, dst} address pairs
+// of the wanted present shards go through the lease's pinned staging into its
+// device buffer in one upload; then the read kernel, then the copies, on the
+// same stream.
+int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
+                        size_t pitch, size_t len, const rsmi::ReadPlan& plan, rsmi::ReadArgs a, hipStream_t s) {
+    const size_t njobs = plan.jobs.size(), count = plan.entries.size(), ncopy = plan.copies.size();
+    size_t max_pid = 0;
+    for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
+    const size_t ent_off = njobs * sizeof(rsmi::ReadJob);
+    const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
+    const size_t pieces_off = round_up(pat_off + njobs * sizeof(uint32_t), 16);
+    const size_t bytes = pieces_off + ncopy * 2 * sizeof(uint64_t);
+    L.begin(s);  // the table buffer's previous readers
+    const bool waited = njobs > 0 && wait_patterns_for(c, L, max_pid, s);
+    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+    if (njobs > 0) {
+        std::memcpy(hb, plan.jobs.data(), ent_off);
+        std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
+        std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+    }
+    uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
+    for (size_t i = 0; i < ncopy; ++i) {
+        const rsmi::ReadCopy& r = plan.copies[i];
+        pieces[2 * i] = r.shard < static_cast<uint32_t>(c->k)
+                            ? reinterpret_cast<uintptr_t>(data) + r.stripe * dss + r.shard * pitch
+                            : reinterpret_cast<uintptr_t>(parity) + r.stripe * pss + (r.shard - c->k) * pitch;
+        pieces[2 * i + 1] = r.dst;
+    }
+    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
+    L.st_stripe.release_after(s);
+    if (e != hipSuccess) {
+        L.end(s);
+        return RS_EDEVICE;
+    }
+    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    if (njobs > 0) {
+        a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
+        a.src = static_cast<const uint32_t*>(c->d_psrc.p);
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(db);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(db + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(db + pat_off);
+        e = rsmi::launch_read(a, s);
+    }
+    // The pieces hold absolute addresses: offsets from a null base.
+    if (e == hipSuccess && ncopy > 0)
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
+                                     static_cast<uint32_t>(ncopy), round_up(len, 16), s);
+    L.end(s);  // under pat_mu: an eviction waits for these launches
+    if (e == hipSuccess) {
+        c->read_regenerated += static_cast<int64_t>(count);
+        c->read_copied += static_cast<int64_t>(ncopy);
+    }
+    if (waited && e == hipSuccess) seen_patterns(c, L);
+    return hip_status(e);
+}
+
+// rs_read_stripes on stream s with lease L: the patterns of the jobs' stripes
+// come from the cache rs_reconstruct_stripes fills, by reconstruct()'s
+// protocol -- lookups and the launch under a shared lock; only a call that
+// meets new patterns takes it exclusively (to create, build and, past the
+// cap, evict).  A plan without jobs (copies only) takes no lock.
+int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                 size_t len, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a, hipStream_t s) {
+    const size_t njobs = plan.jobs.size();
+    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
+    const uint8_t* erased = plan.erased.data();
+    size_t missing = 0;
+    uint64_t gen = 0;
+    {
+        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
+        const int rc = lookup_patterns(c, erased, njobs, L.pid, false, &missing, false, &L.miss_keys);
+        if (rc != RS_OK) return rc;
+        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
+        gen = c->evictions;
+    }
+    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
+    bool stale = c->evictions != gen;
+    if (c->pat_index.size() + missing > c->pat_cap) {
+        evict_patterns(c);
+        stale = true;
+    }
+    const int rc = lookup_patterns(c, erased, njobs, L.pid, true, nullptr, !stale);
+    if (rc != RS_OK) return rc;
+    const int st = flush_patterns(c, s, true);
+    if (st != RS_OK) return st;
+    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
 }
 
 // Holds the least busy member of a device set for one call.
@@ -2524,6 +2618,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (c->set) return rs_kernel_name(rsmi::set_member(c->set, 0), which);
     if (which == 2) return rsmi::verify_variant_name(c->k, c->m);
     if (which == 3) return rsmi::update_variant_name(c->m);
+    if (which == 4) return rsmi::read_variant_name(c->k);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2576,6 +2671,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_MAILBOX_RECOVERED: return c->mailbox_recovered.load();
         case RS_STAT_UPDATE_STRIPES: return c->update_stripes.load();
         case RS_STAT_UPDATE_COPY_COMMITS: return c->update_copy_commits.load();
+        case RS_STAT_READ_REGENERATED: return c->read_regenerated.load();
+        case RS_STAT_READ_COPIED: return c->read_copied.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -2770,6 +2867,52 @@ int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t ps
     LeaseGuard lg(c);
     if (!lg.L) return RS_ENOMEM;
     return update_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
+}
+
+int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch, size_t len,
+                    size_t stripes, const uint8_t* erased, const rs_shard_read* reads, size_t count, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!erased || !reads) return RS_EINVAL;
+    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->set) {
+        rs_ctx* mc = routed(c, data);
+        return mc ? rs_read_stripes(mc, data, dss, parity, pss, pitch, len, stripes, erased, reads, count, stream)
+                  : RS_EINVAL;
+    }
+    // No dst may lie in the call's data or parity region: the stripes are
+    // only read.  A defect of the list, so looked for before the planner
+    // counts any stripe's erasures.
+    const size_t span = round_up(len, 16);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
+    const uintptr_t d1 = d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span;
+    const uintptr_t p1 = c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0;
+    for (size_t i = 0; i < count; ++i) {
+        const uintptr_t t0 = reinterpret_cast<uintptr_t>(reads[i].dst), t1 = t0 + span;
+        if ((t0 < d1 && d0 < t1) || (t0 < p1 && p0 < t1)) return RS_EINVAL;
+    }
+    rsmi::ReadPlan plan;
+    const int rc = rsmi::plan_reads(c->k, c->n, stripes, erased, span, reads, count, &plan);
+    if (rc != RS_OK) return rc;
+    rsmi::ReadArgs a{};
+    a.data = static_cast<const uint8_t*>(data);
+    a.parity = static_cast<const uint8_t*>(parity);
+    a.data_ss = dss;
+    a.parity_ss = pss;
+    a.pitch = pitch;
+    a.ncols16 = static_cast<uint32_t>(span / 16);
+    a.k = static_cast<uint32_t>(c->k);
+    a.m = static_cast<uint32_t>(c->m);
+    a.njobs = static_cast<uint32_t>(plan.jobs.size());
+    a.xcd = c->xcd_split_rec;
+    if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
+    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
+    if (plan.copies.size() * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull) return RS_EINVAL;
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return read_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, a, static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

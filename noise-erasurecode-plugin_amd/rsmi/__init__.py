@@ -38,7 +38,7 @@ EXPORTS = (
     "rs_new", "rs_new_on_device", "rs_free", "rs_k", "rs_n", "rs_device",
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
-    "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes",
+    "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -69,6 +69,18 @@ class ShardUpdate(ctypes.Structure):
 def shard_updates(updates: Sequence[tuple]) -> ctypes.Array:
     """The rs_shard_update table of (stripe, shard, src_ptr) tuples."""
     return (ShardUpdate * len(updates))(*[ShardUpdate(s, i, 0, p) for s, i, p in updates])
+
+
+class ShardRead(ctypes.Structure):
+    """rs_shard_read (include/rsmi.h): one wanted shard and where it goes."""
+
+    _fields_ = [("stripe", ctypes.c_uint64), ("shard", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("dst", ctypes.c_void_p)]
+
+
+def shard_reads(reads: Sequence[tuple]) -> ctypes.Array:
+    """The rs_shard_read table of (stripe, shard, dst_ptr) tuples."""
+    return (ShardRead * len(reads))(*[ShardRead(s, i, 0, p) for s, i, p in reads])
 
 
 class RSError(Exception):
@@ -118,6 +130,7 @@ def _lib() -> ctypes.CDLL:
             "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
             "rs_update_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
+            "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
             "rs_prepare_patterns": (i32, [vp, i32, vp]),
@@ -283,8 +296,8 @@ class FEC:
             pass
 
     def kernel_name(self, which: int = 0) -> str:
-        """Kernel serving encode (0), reconstruct (1), verify (2) or update
-        (3): diagnostics."""
+        """Kernel serving encode (0), reconstruct (1), verify (2), update
+        (3) or degraded read (4): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -450,6 +463,23 @@ class FEC:
                                         pitch, shard_len, stripes, arr, len(updates), stream or None),
                "rs_update_stripes")
 
+    def read_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                     pitch: int, shard_len: int, stripes: int, erased: bytes, reads: Sequence[tuple],
+                     stream: int = 0) -> None:
+        """rs_read_stripes (degraded read): reads is a sequence of (stripe,
+        shard, dst_ptr); the device address dst_ptr receives shard `shard` of
+        stripe `stripe` -- copied if erased (stripes * n flags) says it is
+        present, else computed from the stripe's survivors.  The stripes are
+        only read.  A caller that repeats a large list passes the table
+        shard_reads() built from it instead.  Enqueued on stream."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        arr = reads if isinstance(reads, ctypes.Array) else shard_reads(reads)
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_read_stripes(self._h, data_ptr, data_stride, parity_ptr or None, parity_stride,
+                                      pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), arr,
+                                      len(reads), stream or None), "rs_read_stripes")
+
     def reconstruct_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
                          stream: int = 0) -> None:
         """rs_reconstruct_ptrs: shard i of stripe s at the device address in
@@ -469,7 +499,7 @@ class FEC:
     (STAT_PATTERNS, STAT_EVICTIONS, STAT_BATCHES_IN_PLACE, STAT_BATCHES_STAGED, STAT_LEASES,
      STAT_ENCODES_IN_PLACE, STAT_DECODES_IN_PLACE, STAT_REC_STRIPES_TABLE, STAT_REC_STRIPES_SYNDROME,
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
-     STAT_UPDATE_COPY_COMMITS) = range(14)
+     STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED) = range(16)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
