@@ -72,9 +72,10 @@ int rs_device(const rs_ctx *ctx);
 int rs_encode_matrix(const rs_ctx *ctx, uint8_t *out);
 const char *rs_strerror(int status);
 /* Diagnostics: name of the kernel that serves encode (which = 0),
- * reconstruct (which = 1), verify (which = 2), update (which = 3) or degraded
- * read (which = 4) for this ctx, e.g. "bitslice_k64_m16", "K10_MG4_B256",
- * "verify_K10_MG4_B256", "update_MG4_B256" or "read_K10_MG4_B256" (no
+ * reconstruct (which = 1), verify (which = 2), update (which = 3), degraded
+ * read (which = 4) or degraded check (which = 5) for this ctx, e.g.
+ * "bitslice_k64_m16", "K10_MG4_B256", "verify_K10_MG4_B256",
+ * "update_MG4_B256", "read_K10_MG4_B256" or "check_K10_MG4_B256" (no
  * reference counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
@@ -195,6 +196,47 @@ int rs_verify_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride,
 int rs_correct_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
                        size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
                        size_t stripes, int *status, uint8_t *rewritten, void *stream);
+
+/* Degraded scrub: the two calls above for stripes with missing shards.
+ * Layout and alignment rules as rs_encode_stripes; erased is a HOST array of
+ * stripes * n flags as for rs_reconstruct_stripes, not retained.  The slots
+ * of erased shards are never dereferenced, for reading or writing.
+ *
+ * rs_verify_degraded: first_bad[s] (DEVICE, as for rs_verify_stripes) = the
+ * lowest byte offset o < shard_len at which the PRESENT shards of stripe s do
+ * not lie on one codeword, or RS_VERIFY_CLEAN.  For a stripe with e erasures
+ * the k survivors Rebuild chooses recompute the other m - e present shards,
+ * which are compared with the stored ones; the code is MDS, so the verdict
+ * does not depend on that choice, and with e == 0 it is rs_verify_stripes'
+ * (with no flag set at all the call is rs_verify_stripes).  A stripe with
+ * exactly m erasures has no redundancy left: RS_VERIFY_CLEAN.  More than m
+ * erasures in any stripe -> RS_ENOT_ENOUGH: nothing is launched and first_bad
+ * is not written.  RS_EINVAL for NULL erased or first_bad and for what
+ * rs_verify_stripes refuses, or stripes >= 2^32; stripes == 0 or
+ * shard_len == 0: RS_OK.  Reads data and parity only; writes nothing but
+ * first_bad.  A degraded stripe moves (k + m - e) * S bytes.  Enqueued on
+ * stream; returns when queued (the small job tables are staged through pinned
+ * memory).
+ *
+ * rs_correct_degraded: rs_correct_stripes with the erasures known from the
+ * start.  Repairs every stripe with e erasures in which at most
+ * floor((m - e) / 2) present shards hold wrong bytes, however many bytes and
+ * wherever in those shards, by regenerating the located shards in place.  The
+ * erased shards are NOT filled in (rs_reconstruct_stripes with the same flags
+ * does that afterwards).  status and rewritten as for rs_correct_stripes;
+ * rewritten is set for located shards only, never for erased ones.  An
+ * inconsistent stripe with m - e < 2 ends RS_ETOO_MANY_ERRORS with nothing in
+ * it written.  More than m erasures in any stripe -> RS_ENOT_ENOUGH: nothing
+ * is launched or written.  Synchronous like rs_correct_stripes; with no flag
+ * set it is rs_correct_stripes. */
+int rs_verify_degraded(rs_ctx *ctx, const void *data, size_t data_stripe_stride,
+                       const void *parity, size_t parity_stripe_stride, size_t shard_pitch,
+                       size_t shard_len, size_t stripes, const uint8_t *erased,
+                       uint32_t *first_bad, void *stream);
+int rs_correct_degraded(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                        size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                        size_t stripes, const uint8_t *erased, int *status,
+                        uint8_t *rewritten, void *stream);
 
 /* In-place parity update: overwrite data shards of stripes that already hold
  * parity and patch that parity from the difference alone.  Layout and
@@ -318,6 +360,8 @@ enum {
     RS_STAT_UPDATE_COPY_COMMITS = 13, /* rs_update_stripes calls whose data commit ran as a separate copy pass */
     RS_STAT_READ_REGENERATED = 14, /* shards regenerated by rs_read_stripes            */
     RS_STAT_READ_COPIED = 15,      /* shards rs_read_stripes served by copy            */
+    RS_STAT_CHECK_STRIPES = 16,    /* degraded stripes checked by the check kernel (rs_verify_degraded, rs_correct_degraded) */
+    RS_STAT_SCRUB_REGENERATED = 17, /* shards regenerated by rs_correct_degraded       */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -421,8 +465,8 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
- *    rs_reconstruct_ptrs, rs_fill_splitmix, rs_blake2b_device) run on a
- *    member on the device that holds their (first) device buffer, RS_EINVAL
+ *    rs_verify_degraded, rs_correct_degraded, rs_reconstruct_ptrs,
+ *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;
  *  - rs_stat / rs_pattern_count / rs_pattern_evictions are summed over the

@@ -1,0 +1,82 @@
+// check_plan.cpp -- see check_plan.hpp.
+#include "check_plan.hpp"
+
+#include <algorithm>
+
+namespace rsmi {
+
+namespace {
+void clear(CheckPlan* plan) {
+    plan->intact.clear();
+    plan->jobs.clear();
+    plan->entries.clear();
+    plan->flags.clear();
+    plan->saturated = 0;
+    plan->max_j = 0;
+}
+}  // namespace
+
+int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                const CheckLayout& lay, CheckPlan* plan) {
+    if (!plan) return RS_EINVAL;
+    clear(plan);
+    if (k < 1 || n < k || n > 256 || stripes > 0xFFFFFFFFull) return RS_EINVAL;
+    const size_t total = list ? count : stripes;
+    if (total == 0) return RS_OK;
+    if (!erased) return RS_EINVAL;
+    const int m = n - k;
+    for (size_t i = 0; i < total; ++i) {
+        const uint32_t stripe = list ? list[i] : static_cast<uint32_t>(i);
+        if (list && (stripe >= stripes || (i > 0 && list[i - 1] >= stripe))) {
+            clear(plan);
+            return RS_EINVAL;
+        }
+        const uint8_t* fl = erased + static_cast<size_t>(stripe) * static_cast<size_t>(n);
+        int e = 0;
+        for (int id = 0; id < n; ++id) e += fl[id] != 0;
+        if (e > m) {
+            clear(plan);
+            return RS_ENOT_ENOUGH;
+        }
+        if (e == 0) {
+            plan->intact.push_back(stripe);
+            continue;
+        }
+        if (e == m) {
+            ++plan->saturated;
+            continue;
+        }
+        // Rebuild takes every present data share and fills up to k with the
+        // highest-numbered present parity: the m - e present parity shards it
+        // leaves out, the lowest-numbered ones, are U (always parity shards).
+        const int j = m - e;
+        plan->jobs.push_back(ReadJob{stripe, static_cast<uint32_t>(plan->entries.size()), static_cast<uint32_t>(j)});
+        plan->max_j = std::max(plan->max_j, static_cast<uint32_t>(j));
+        const size_t f0 = plan->flags.size();
+        plan->flags.resize(f0 + static_cast<size_t>(n));
+        uint8_t* xf = &plan->flags[f0];
+        int left = j;  // shards of U still to come
+        for (int id = 0; id < n; ++id) {
+            xf[id] = fl[id] != 0 ? 1 : 0;
+            if (id >= k && !xf[id] && left > 0) {
+                xf[id] = 1;
+                --left;
+            }
+        }
+        // Entries in id order; the rank of an id of U is the number of ids of
+        // X' below it, counted in the same walk.
+        uint32_t rank = 0;
+        for (int id = 0; id < n; ++id) {
+            if (!xf[id]) continue;
+            if (!fl[id]) {
+                const uint64_t at = lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
+                                    static_cast<uint64_t>(id - k) * lay.pitch;
+                plan->entries.push_back(ReadEntry{at, rank, 0u});
+            }
+            ++rank;
+        }
+    }
+    return RS_OK;
+}
+
+}  // namespace rsmi

@@ -1,0 +1,50 @@
+// check_plan.hpp -- host-side planner of rs_verify_degraded / rs_correct_degraded
+// (the scrub of device-resident stripes with missing shards): counts every
+// stripe's erasures, splits the stripes into intact, degraded and saturated
+// ones, and turns each degraded stripe into one job of the check kernel.
+// Pure host code: no HIP, no context.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/rsmi.h"
+#include "read_plan.hpp"
+
+namespace rsmi {
+
+// The strided layout of rs_encode_stripes, as addresses.
+struct CheckLayout {
+    uint64_t data, parity;               // device addresses of the two regions
+    uint64_t data_ss, parity_ss, pitch;  // stripe strides and shard pitch (bytes)
+};
+
+// A degraded stripe with erasure set X, |X| = e, 1 <= e < m, is checked
+// against the k survivors C that Rebuild chooses for X (data shares first,
+// then the highest-numbered parity): its present shards lie on one codeword
+// iff every shard of U = present \ C equals its value computed from C.  The
+// decode pattern of the erasure set X' = X + U (exactly m ids, the same
+// survivors C) holds those rows: row t regenerates the t-th id of X'.
+struct CheckPlan {
+    std::vector<uint32_t> intact;    // stripes without erasures, increasing: the verify kernel's
+    std::vector<ReadJob> jobs;       // one per degraded stripe, in stripe order
+    std::vector<ReadEntry> entries;  // a job's entries are its shards of U in id order:
+                                     // {dst = address of the stored shard, row = rank of the id in X'}
+    std::vector<uint8_t> flags;      // [jobs.size()][n]: X' of every job, 0 / 1
+    size_t saturated = 0;            // stripes with exactly m erasures (and m > 0): nothing to check
+    uint32_t max_j = 0;              // the largest j = m - e of any job
+};
+
+// Plans the check of RS(k, n) stripes [0, stripes) -- or, with list != nullptr,
+// of the `count` stripes list[0 .. count), strictly increasing -- with the
+// erasure flags erased[stripes][n] (non-zero = missing; only the flags of the
+// planned stripes are examined).  RS_OK and the plan, or, with the plan left
+// empty:
+//   RS_EINVAL       plan or erased NULL, k < 1, n < k, n > 256, stripes >= 2^32,
+//                   a listed stripe >= stripes or out of order
+//   RS_ENOT_ENOUGH  a planned stripe has more than n - k erasures
+int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                const CheckLayout& lay, CheckPlan* plan);
+
+}  // namespace rsmi

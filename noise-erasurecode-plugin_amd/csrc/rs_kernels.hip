@@ -427,6 +427,26 @@ __global__ __launch_bounds__(64) void gather_columns_kernel(const uint8_t* data,
     }
 }
 
+// The gather of the degraded scrub: pair i also has n flags, flags[i * n + id]
+// non-zero = shard id is missing.  Its byte is written as 0 and no address
+// into its slot is formed (scrub_locate ignores those positions).
+__global__ __launch_bounds__(64) void gather_columns_masked_kernel(const uint8_t* data, const uint8_t* parity,
+                                                                   uint64_t data_ss, uint64_t parity_ss,
+                                                                   uint64_t pitch, uint32_t k, uint32_t n,
+                                                                   const uint2* pairs, const uint8_t* flags,
+                                                                   uint8_t* out) {
+    const uint2 p = pairs[blockIdx.x];
+    for (uint32_t id = threadIdx.x; id < n; id += 64u) {
+        uint8_t v = 0;
+        if (!flags[static_cast<size_t>(blockIdx.x) * n + id]) {
+            const uint8_t* shard = id < k ? data + p.x * data_ss + static_cast<uint64_t>(id) * pitch
+                                          : parity + p.x * parity_ss + static_cast<uint64_t>(id - k) * pitch;
+            v = shard[p.y];
+        }
+        out[static_cast<size_t>(blockIdx.x) * n + id] = v;
+    }
+}
+
 // In-place parity update (rs_kernels.hpp UpdArgs): matmul_block's block
 // decomposition with the job's j changed shards as the runtime "k".  The
 // accumulators start as the stored parity columns (as in the verify twin),
@@ -718,6 +738,183 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
     }
 }
 
+// Degraded check (rs_kernels.hpp launch_check): the verify twin of
+// rs_read_kernel, with a body of its own.  A job's entries are the stripe's
+// present shards outside the pattern's survivors; entries[..].dst is the
+// address of the STORED shard and is only read.  The block loads the stored
+// 16-byte columns of its group's rows behind the survivor loads and before
+// the table build, into the accumulators (as matmul_block<VF>): after the
+// MACs an accumulator holds stored ^ recomputed, and the first mismatching
+// lane of a wave does one atomicMin on first_bad[stripe].  Nothing else is
+// stored; the slots of erased shards are in neither the pattern's survivors
+// nor the entries, so no address into them is ever formed.
+// LDS: [k][20] table dwords | k survivor pointers.
+template <int K, int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_check_kernel(ReadArgs a, uint32_t* first_bad, uint32_t shard_len) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
+    constexpr bool kRegPtrs = K > 0 && K <= 16;           // survivor bases kept in SGPRs
+    constexpr int JB = (K == 0) ? 8 : (K <= 16 ? K : 8);  // survivor loads in flight
+    const int k = K ? K : static_cast<int>(a.k);
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * kStepWords);
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const uint64_t ji = b / a.chunks;
+    const ReadJob job = a.jobs[ji];
+    // Stripe indices of a check fit 32 bits (plan_checks).
+    const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe)));
+    const int j = __builtin_amdgcn_readfirstlane(job.j);
+    const int row0 = static_cast<int>(grp) * MG;
+    if (row0 >= j) return;  // whole block: uniform
+    const int eg = min(MG, j - row0);
+    const ReadEntry* ent = a.entries + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.first)) + row0;
+    const uint32_t pat = __builtin_amdgcn_readfirstlane(a.pats[ji]);
+
+    // This lane's coefficient byte for the table build is requested first, so
+    // waiting for it later does not wait for the survivor loads behind it.
+    const uint8_t* coef = a.coef + static_cast<size_t>(pat) * a.m * k;
+    constexpr bool one_coef = (K > 0 && K * MG <= BT);
+    uint32_t cbyte = 0u;
+    if constexpr (one_coef) {
+        const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+        if (static_cast<int>(threadIdx.x) < k * MG && t < eg) cbyte = coef[static_cast<size_t>(ent[t].row) * k + c];
+    }
+
+    const uint32_t* srcid = a.src + static_cast<size_t>(pat) * k;
+    uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
+    uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
+    uint8_t* sp[kRegPtrs ? K : 1];
+    if constexpr (kRegPtrs) {
+        uint32_t ids[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
+                                                     : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+    } else {
+        for (int i = threadIdx.x; i < k; i += BT) {
+            const uint32_t id = srcid[i];
+            sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                               : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+        }
+    }
+    const uint32_t last = a.ncols16 - 1;
+    // Survivor loads of the block's first iteration go out before the table
+    // build, as in matmul_block.
+    uint4 xpre[kRegPtrs ? K : 1];
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    if constexpr (kRegPtrs) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + off0);
+    }
+    // Stored shards of the group's rows; rows past eg have none.
+    const uint8_t* dp[MG];
+#pragma unroll
+    for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(ent[t].dst)) : nullptr;
+    // The accumulators start as the stored columns, loaded next to the
+    // survivors so they ride the same latency.  Rows past eg are not read and
+    // stay zero (they are not multiplied either, so they never report).
+    uint32_t acc[kRowsPerStep][4];
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int r = 0; r < kRowsPerStep; ++r) {
+            uint4 p = make_uint4(0u, 0u, 0u, 0u);
+            if (r < eg) p = gload16<NT>(dp[r] + at);
+            acc[r][0] = p.x;
+            acc[r][1] = p.y;
+            acc[r][2] = p.z;
+            acc[r][3] = p.w;
+        }
+    };
+    load_stored(off0);
+    // Split tables of the group's rows: survivor c's sub-step holds 4 x 5 dwords.
+    if constexpr (one_coef) {
+        if (static_cast<int>(threadIdx.x) < k * MG) {
+            const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+            build_tables(cbyte, &tw[c * kStepWords + t * 5]);
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < k * MG; idx += BT) {
+            const int c = idx / MG, t = idx - c * MG;
+            const uint32_t cf = (t < eg) ? coef[static_cast<size_t>(ent[t].row) * k + c] : 0u;
+            build_tables(cf, &tw[c * kStepWords + t * 5]);
+        }
+    }
+    __syncthreads();
+
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;  // tail lanes re-read the last column (always in bounds) and do not report
+
+        for (int jb = 0; jb < k; jb += JB) {
+            uint4 xb[kRegPtrs ? 1 : JB];
+            uint4* x = kRegPtrs ? xpre : xb;
+            if constexpr (!kRegPtrs) {
+                const uint32_t off = (ok ? col : last) * 16u;
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (K == 0 && jb + q >= k) break;
+                    x[q] = gload16<NT>(uniform_ptr(sptr[jb + q]) + off);
+                }
+            }
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (K == 0 && jb + q >= k) break;
+                const bool more = q + 1 < JB && (K != 0 || jb + q + 1 < k);
+                if (more) load_step(lds4 + static_cast<size_t>(jb + q + 1) * (kStepWords / 4), TB);
+                mac_step_rows(acc, x[q], TA, eg);
+                step_fence(acc);
+#pragma unroll
+                for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+            }
+        }
+        const bool again = it + 1 < a.iters && colbase + cstride < a.ncols16;
+        const uint32_t ncol = colbase + cstride + threadIdx.x;
+        const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
+        if constexpr (kRegPtrs) {
+            // Software pipelining: the next iteration's survivor loads go out
+            // before this iteration's compare.
+            if (again) {
+#pragma unroll
+                for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + noff);
+            }
+        }
+        // Bytes at which any row's stored column differs from the recomputed
+        // one; tail lanes and bytes past shard_len do not count.
+        uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < kRowsPerStep; ++r)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) d[w] |= acc[r][w];
+        const uint32_t nb = ok ? min(16u, shard_len - col * 16u) : 0u;  // bytes of this column below shard_len
+        uint32_t byte = 16u;
+#pragma unroll
+        for (int w = 3; w >= 0; --w) {
+            const uint32_t nbw = nb > 4u * w ? min(4u, nb - 4u * w) : 0u;
+            const uint32_t dw = d[w] & (nbw >= 4u ? ~0u : (1u << (8u * nbw)) - 1u);
+            if (dw) byte = 4u * w + (static_cast<uint32_t>(__builtin_ctz(dw)) >> 3);
+        }
+        // Lanes are in column order: the first mismatching lane holds the
+        // wave's lowest offset.
+        const bool bad = byte < 16u;
+        const uint64_t bal = __ballot(bad);
+        if (bad && (bal & ((1ull << __lane_id()) - 1ull)) == 0) atomicMin(&first_bad[s], col * 16u + byte);
+        if (again) load_stored(noff);
+    }
+}
+
 template <int K, int MG, int BT, bool NT>
 __global__ __launch_bounds__(BT) void rs_matmul_kernel(MatArgs a) {
     extern __shared__ uint4 lds4[];
@@ -946,11 +1143,39 @@ const ReadVariant& pick_read(int k) {
     return kRead[sizeof(kRead) / sizeof(kRead[0]) - 1];  // runtime k
 }
 
+// Check variants: the read kernel's instances, one twin each.
+struct CheckVariant {
+    int K;
+    const char* name;
+    void (*fn)(ReadArgs, uint32_t*, uint32_t);
+};
+#define RS_CHECK(K) {K, "check_K" #K "_MG4_B256", rs_check_kernel<K, 4, kBlock, true>}
+const CheckVariant kCheck[] = {RS_CHECK(10), RS_CHECK(4), RS_CHECK(8), RS_CHECK(64), RS_CHECK(0)};
+#undef RS_CHECK
+
+const CheckVariant& pick_check(int k) {
+    for (const CheckVariant& v : kCheck)
+        if (v.K == k) return v;
+    return kCheck[sizeof(kCheck) / sizeof(kCheck[0]) - 1];  // runtime k
+}
+
 }  // namespace
 
 const char* update_variant_name(int m) { return pick_update(m, 0).name; }
 
 const char* read_variant_name(int k) { return pick_read(k).name; }
+
+const char* check_variant_name(int k) { return pick_check(k).name; }
+
+hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    const CheckVariant& v = pick_check(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a, first_bad, shard_len);
+    return hipGetLastError();
+}
 
 bool plan_read(ReadArgs* a, uint32_t max_j) {
     const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
@@ -1087,6 +1312,14 @@ hipError_t launch_gather_columns(const MatArgs& a, const uint2* pairs, uint32_t 
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(gather_columns_kernel, dim3(count), dim3(64), 0, stream, a.data, a.parity, a.data_ss,
                        a.parity_ss, a.pitch, a.k, a.k + a.m, pairs, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_columns_masked(const MatArgs& a, const uint2* pairs, const uint8_t* flags, uint32_t count,
+                                        uint8_t* out, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_columns_masked_kernel, dim3(count), dim3(64), 0, stream, a.data, a.parity, a.data_ss,
+                       a.parity_ss, a.pitch, a.k, a.k + a.m, pairs, flags, out);
     return hipGetLastError();
 }
 

@@ -180,11 +180,26 @@ bool plan_read(ReadArgs* a, uint32_t max_j);
 hipError_t launch_read(const ReadArgs& a, hipStream_t stream);  // a: planned
 const char* read_variant_name(int k);  // "read_K10_MG4_B256" etc.
 
+// Degraded check (rs_verify_degraded): the verify twin of the read launch,
+// with the same arguments and plan (plan_read).  Job b's entries are the
+// present shards of its stripe that the pattern pats[b] does not use as
+// survivors: entries[..].dst is the address of the STORED shard, .row the
+// pattern row that recomputes it.  The kernel compares the two in registers
+// and first_bad[stripe] (device, preset to 0xFF bytes on `stream` by the
+// caller) receives by atomicMin the lowest byte offset below shard_len at
+// which they differ.  Everything is only read: (k + j) * S bytes per job.
+hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream);  // a: planned
+const char* check_variant_name(int k);  // "check_K10_MG4_B256" etc.
+
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard
 // id, for every shard of the stripe (a: strided layout, k, m).
 hipError_t launch_gather_columns(const MatArgs& a, const uint2* pairs, uint32_t count, uint8_t* out,
                                  hipStream_t stream);
+// The same with missing shards: flags[i * n + id] (device) non-zero = shard id
+// of pair i's stripe is missing; out gets 0 there and the slot is not read.
+hipError_t launch_gather_columns_masked(const MatArgs& a, const uint2* pairs, const uint8_t* flags, uint32_t count,
+                                        uint8_t* out, hipStream_t stream);
 
 // Device-side copy of `count` pieces of `bytes` bytes (a multiple of 16):
 // piece i copies src + pieces[2i] to dst + pieces[2i+1] (16-byte aligned

@@ -29,6 +29,7 @@
 
 #include "bitslice.hpp"
 #include "blake2b.hpp"
+#include "check_plan.hpp"
 #include "device_set.hpp"
 #include "gf256.hpp"
 #include "gf_invert.hpp"
@@ -365,6 +366,7 @@ struct rs_ctx {
     std::atomic<int64_t> mailbox_calls{0}, mailbox_recovered{0};         // MailboxCall (rs_stat)
     std::atomic<int64_t> update_stripes{0}, update_copy_commits{0};      // rs_update_stripes (rs_stat)
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
+    std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1237,6 +1239,24 @@ int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, si
 }
 
 // --------------------------------------------------------- degraded read ----
+// The read kernel's arguments for `njobs` jobs over the strided layout (the
+// launch plan and the device tables are filled in later).
+rsmi::ReadArgs read_args(const rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                         size_t len, size_t njobs) {
+    rsmi::ReadArgs a{};
+    a.data = static_cast<const uint8_t*>(data);
+    a.parity = static_cast<const uint8_t*>(parity);
+    a.data_ss = dss;
+    a.parity_ss = pss;
+    a.pitch = pitch;
+    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
+    a.k = static_cast<uint32_t>(c->k);
+    a.m = static_cast<uint32_t>(c->m);
+    a.njobs = static_cast<uint32_t>(njobs);
+    a.xcd = c->xcd_split_rec;
+    return a;
+}
+
 // Launches a planned rs_read_stripes on stream s.  With jobs, pat_mu is held
 // (shared or exclusive) and L.pid holds the built pattern of every job.  The
 // job and entry tables, the jobs' pattern ids and the {src, dst} address pairs
@@ -1244,7 +1264,8 @@ int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, si
 // device buffer in one upload; then the read kernel, then the copies, on the
 // same stream.
 int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
-                        size_t pitch, size_t len, const rsmi::ReadPlan& plan, rsmi::ReadArgs a, hipStream_t s) {
+                        size_t pitch, size_t len, const rsmi::ReadPlan& plan, rsmi::ReadArgs a, hipStream_t s,
+                        bool scrub = false) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size(), ncopy = plan.copies.size();
     size_t max_pid = 0;
     for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
@@ -1289,7 +1310,9 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const
         e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
                                      static_cast<uint32_t>(ncopy), round_up(len, 16), s);
     L.end(s);  // under pat_mu: an eviction waits for these launches
-    if (e == hipSuccess) {
+    if (e == hipSuccess && scrub) {
+        c->scrub_regenerated += static_cast<int64_t>(count);
+    } else if (e == hipSuccess) {
         c->read_regenerated += static_cast<int64_t>(count);
         c->read_copied += static_cast<int64_t>(ncopy);
     }
@@ -1301,11 +1324,14 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const
 // come from the cache rs_reconstruct_stripes fills, by reconstruct()'s
 // protocol -- lookups and the launch under a shared lock; only a call that
 // meets new patterns takes it exclusively (to create, build and, past the
-// cap, evict).  A plan without jobs (copies only) takes no lock.
+// cap, evict).  A plan without jobs (copies only) takes no lock.  scrub: the
+// call regenerates located shards for rs_correct_degraded, which counts them
+// in a counter of its own.
 int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
-                 size_t len, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a, hipStream_t s) {
+                 size_t len, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a, hipStream_t s,
+                 bool scrub = false) {
     const size_t njobs = plan.jobs.size();
-    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
+    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
     const uint8_t* erased = plan.erased.data();
     size_t missing = 0;
     uint64_t gen = 0;
@@ -1313,7 +1339,7 @@ int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* 
         std::shared_lock<std::shared_mutex> rl(c->pat_mu);
         const int rc = lookup_patterns(c, erased, njobs, L.pid, false, &missing, false, &L.miss_keys);
         if (rc != RS_OK) return rc;
-        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
+        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
         gen = c->evictions;
     }
     std::unique_lock<std::shared_mutex> wl(c->pat_mu);
@@ -1326,7 +1352,224 @@ int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* 
     if (rc != RS_OK) return rc;
     const int st = flush_patterns(c, s, true);
     if (st != RS_OK) return st;
-    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s);
+    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
+}
+
+// ------------------------------------------------------- degraded scrub ----
+// Launches a planned degraded verify on stream s.  With jobs, pat_mu is held
+// (shared or exclusive) and L.pid holds the built pattern of every job.  The
+// intact stripes' list, the job and entry tables and the jobs' pattern ids go
+// through the lease's pinned staging into its device buffer in one upload;
+// then first_bad's preset and the verify kernel over the intact stripes
+// (launch_verify_stripes), then the check kernel over the degraded ones.
+int launch_check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
+                         size_t pitch, size_t len, size_t stripes, const rsmi::CheckPlan& plan, rsmi::ReadArgs a,
+                         uint32_t* first_bad, hipStream_t s) {
+    const size_t nintact = plan.intact.size(), njobs = plan.jobs.size(), count = plan.entries.size();
+    size_t max_pid = 0;
+    for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
+    const size_t job_off = round_up(nintact * sizeof(uint2), 16);
+    const size_t ent_off = job_off + njobs * sizeof(rsmi::ReadJob);
+    const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
+    const size_t bytes = pat_off + njobs * sizeof(uint32_t);
+    L.begin(s);  // the table buffer's previous readers
+    const bool waited = njobs > 0 && wait_patterns_for(c, L, max_pid, s);
+    hipError_t e = hipSuccess;
+    if (bytes > 0) {
+        if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+        uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+        uint2* desc = reinterpret_cast<uint2*>(hb);
+        for (size_t i = 0; i < nintact; ++i) desc[i] = make_uint2(plan.intact[i], static_cast<uint32_t>(c->m));
+        if (njobs > 0) {
+            std::memcpy(hb + job_off, plan.jobs.data(), njobs * sizeof(rsmi::ReadJob));
+            std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
+            std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+        }
+        e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
+        L.st_stripe.release_after(s);
+        if (e != hipSuccess) {
+            L.end(s);
+            return RS_EDEVICE;
+        }
+    }
+    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    int rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, reinterpret_cast<const uint2*>(db),
+                                   nintact, first_bad, s);
+    if (rc == RS_OK && njobs > 0) {
+        a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
+        a.src = static_cast<const uint32_t*>(c->d_psrc.p);
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(db + job_off);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(db + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(db + pat_off);
+        rc = hip_status(rsmi::launch_check(a, first_bad, static_cast<uint32_t>(len), s));
+    }
+    L.end(s);  // under pat_mu: an eviction waits for these launches
+    if (rc == RS_OK) c->check_stripes += static_cast<int64_t>(njobs);
+    if (waited && rc == RS_OK) seen_patterns(c, L);
+    return rc;
+}
+
+// A planned degraded verify on stream s with lease L: the patterns of the
+// jobs' compact flags (the erasure sets X') come from the cache
+// rs_reconstruct_stripes fills, by read_stripes()'s protocol.  A plan without
+// jobs takes no lock.
+int check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                  size_t len, size_t stripes, const rsmi::CheckPlan& plan, uint32_t* first_bad, hipStream_t s) {
+    const size_t njobs = plan.jobs.size();
+    rsmi::ReadArgs a = read_args(c, data, dss, parity, pss, pitch, len, njobs);
+    if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
+    if (njobs == 0) return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
+    const uint8_t* flags = plan.flags.data();
+    size_t missing = 0;
+    uint64_t gen = 0;
+    {
+        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
+        const int rc = lookup_patterns(c, flags, njobs, L.pid, false, &missing, false, &L.miss_keys);
+        if (rc != RS_OK) return rc;
+        if (missing == 0)
+            return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
+        gen = c->evictions;
+    }
+    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
+    bool stale = c->evictions != gen;
+    if (c->pat_index.size() + missing > c->pat_cap) {
+        evict_patterns(c);
+        stale = true;
+    }
+    const int rc = lookup_patterns(c, flags, njobs, L.pid, true, nullptr, !stale);
+    if (rc != RS_OK) return rc;
+    const int st = flush_patterns(c, s, true);
+    if (st != RS_OK) return st;
+    return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
+}
+
+// rs_correct_degraded on stream s with lease L: correct_stripes' loop with
+// the erasure sets X known from the start.  Device workspace (L.d_scrub) and
+// its pinned mirror (L.st_scrub), all O(stripes):
+//   first_bad u32 [stripes] | list uint2 [stripes] | columns u8 [stripes * n] | flags u8 [stripes * n]
+// `list` holds the gather's {stripe, byte offset} pairs and `flags` the X of
+// the same live stripes.  The verifies go through check_stripes over the live
+// list; the located set L of a stripe is regenerated in place by the read
+// path with the flags X + L, wanted L and every dst the shard's own slot, so
+// the slots of X are neither read nor written.
+int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                     size_t stripes, const uint8_t* erased, int* status, uint8_t* rewritten, hipStream_t s) {
+    const size_t n = static_cast<size_t>(c->n);
+    const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
+    const size_t cols_off = list_off + stripes * sizeof(uint2);
+    const size_t flag_off = cols_off + stripes * n;
+    const size_t bytes = flag_off + stripes * n;
+    L.begin(s);
+    if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_scrub.p);
+    uint8_t* const db = static_cast<uint8_t*>(L.d_scrub.p);
+    uint32_t* const h_fb = reinterpret_cast<uint32_t*>(hb);
+    uint2* const h_list = reinterpret_cast<uint2*>(hb + list_off);
+    uint8_t* const h_cols = hb + cols_off;
+    uint8_t* const h_flags = hb + flag_off;
+    uint32_t* const d_fb = reinterpret_cast<uint32_t*>(db);
+    uint2* const d_list = reinterpret_cast<uint2*>(db + list_off);
+    uint8_t* const d_cols = db + cols_off;
+    uint8_t* const d_flags = db + flag_off;
+    // Every exit records the lease's last device use.
+    struct End {
+        Lease& L;
+        hipStream_t s;
+        ~End() { L.end(s); }
+    } end_guard{L, s};
+
+    const rsmi::CheckLayout lay{reinterpret_cast<uintptr_t>(data), reinterpret_cast<uintptr_t>(parity), dss, pss,
+                                pitch};
+    rsmi::CheckPlan cp;
+    // Degraded verify of all stripes (list == nullptr) or the listed ones, and
+    // the verdicts to the host.
+    auto verify = [&](const uint32_t* list, size_t count) -> int {
+        int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, lay, &cp);
+        if (rc == RS_OK) rc = check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, cp, d_fb, s);
+        if (rc != RS_OK) return rc;
+        if (hipMemcpyAsync(h_fb, d_fb, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return RS_EDEVICE;
+        return RS_OK;
+    };
+    int rc = verify(nullptr, 0);
+    if (rc != RS_OK) return rc;
+    std::vector<uint32_t> live;
+    for (size_t i = 0; i < stripes; ++i)
+        if (h_fb[i] != RS_VERIFY_CLEAN) live.push_back(static_cast<uint32_t>(i));
+    if (live.empty()) return RS_OK;
+
+    // known: X plus every shard located so far (the set L of the stripe;
+    // `rewritten` reports known minus X).
+    std::vector<uint8_t> known(stripes * n);
+    for (size_t i = 0; i < stripes * n; ++i) known[i] = erased[i] != 0 ? 1 : 0;
+    bool failed = false;
+    auto give_up = [&](uint32_t i) {
+        if (status) status[i] = RS_ETOO_MANY_ERRORS;
+        failed = true;
+    };
+    const rsmi::MatArgs ga = base_args(c, data, dss, parity, pss, pitch, len, stripes);
+    const size_t span = round_up(len, 16);
+    std::vector<rs_shard_read> reads;
+    rsmi::ReadPlan rp;
+    for (int round = 0; round < c->m && !live.empty(); ++round) {
+        // The column at each live stripe's first inconsistent offset, without
+        // the missing shards.
+        for (size_t j = 0; j < live.size(); ++j) {
+            if (h_fb[live[j]] >= len) return RS_EDEVICE;  // never: the check reports offsets below shard_len
+            h_list[j] = make_uint2(live[j], h_fb[live[j]]);
+            for (size_t id = 0; id < n; ++id) h_flags[j * n + id] = erased[live[j] * n + id] != 0 ? 1 : 0;
+        }
+        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_flags, h_flags, live.size() * n, hipMemcpyHostToDevice, s) != hipSuccess ||
+            rsmi::launch_gather_columns_masked(ga, d_list, d_flags, static_cast<uint32_t>(live.size()), d_cols, s) !=
+                hipSuccess ||
+            hipMemcpyAsync(h_cols, d_cols, live.size() * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return RS_EDEVICE;
+        size_t kept = 0;
+        reads.clear();
+        for (size_t j = 0; j < live.size(); ++j) {
+            const uint32_t i = live[j];
+            uint8_t* kn = &known[static_cast<size_t>(i) * n];
+            // An inconsistent column always holds a wrong share outside the
+            // set, so a round that locates none is a failure too.
+            if (rsmi::scrub_locate(c->k, c->n, kn, h_cols + j * n) <= 0) {
+                give_up(i);
+                continue;
+            }
+            for (size_t id = 0; id < n; ++id) {
+                if (!kn[id] || erased[static_cast<size_t>(i) * n + id]) continue;
+                uint8_t* slot = id < static_cast<size_t>(c->k)
+                                    ? static_cast<uint8_t*>(data) + i * dss + id * pitch
+                                    : static_cast<uint8_t*>(parity) + i * pss + (id - c->k) * pitch;
+                reads.push_back(rs_shard_read{i, static_cast<uint32_t>(id), 0u, slot});
+            }
+            live[kept++] = i;
+        }
+        live.resize(kept);
+        if (live.empty()) break;
+        // All of every live stripe's located set, in one batched read into place.
+        rc = rsmi::plan_reads(c->k, c->n, stripes, known.data(), span, reads.data(), reads.size(), &rp);
+        if (rc != RS_OK) return rc;
+        rsmi::ReadArgs ra = read_args(c, data, dss, parity, pss, pitch, len, rp.jobs.size());
+        if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
+        rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, true);
+        if (rc != RS_OK) return rc;
+        if (rewritten)
+            for (uint32_t i : live)
+                for (size_t id = 0; id < n; ++id)
+                    rewritten[i * n + id] = known[i * n + id] && !erased[i * n + id] ? 1 : 0;
+        // Verify the live stripes again.
+        rc = verify(live.data(), live.size());
+        if (rc != RS_OK) return rc;
+        kept = 0;
+        for (uint32_t i : live)
+            if (h_fb[i] != RS_VERIFY_CLEAN) live[kept++] = i;
+        live.resize(kept);
+    }
+    for (uint32_t i : live) give_up(i);  // still inconsistent after m rounds
+    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
 }
 
 // Holds the least busy member of a device set for one call.
@@ -2619,6 +2862,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 2) return rsmi::verify_variant_name(c->k, c->m);
     if (which == 3) return rsmi::update_variant_name(c->m);
     if (which == 4) return rsmi::read_variant_name(c->k);
+    if (which == 5) return rsmi::check_variant_name(c->k);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2673,6 +2917,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_UPDATE_COPY_COMMITS: return c->update_copy_commits.load();
         case RS_STAT_READ_REGENERATED: return c->read_regenerated.load();
         case RS_STAT_READ_COPIED: return c->read_copied.load();
+        case RS_STAT_CHECK_STRIPES: return c->check_stripes.load();
+        case RS_STAT_SCRUB_REGENERATED: return c->scrub_regenerated.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -2838,6 +3084,67 @@ int rs_correct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t p
                            static_cast<hipStream_t>(stream));
 }
 
+int rs_verify_degraded(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                       size_t len, size_t stripes, const uint8_t* erased, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!erased || !first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->set) {
+        rs_ctx* mc = routed(c, c->m > 0 ? data : first_bad);
+        return mc ? rs_verify_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, first_bad, stream)
+                  : RS_EINVAL;
+    }
+    const rsmi::CheckLayout lay{reinterpret_cast<uintptr_t>(data), reinterpret_cast<uintptr_t>(parity), dss, pss,
+                                pitch};
+    rsmi::CheckPlan plan;
+    const int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, nullptr, 0, lay, &plan);
+    if (rc != RS_OK) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    // No flag set: rs_verify_stripes' launch, without a lock or a lease.
+    if (plan.intact.size() == stripes)
+        return launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, first_bad,
+                                     static_cast<hipStream_t>(stream));
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return check_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, plan, first_bad,
+                         static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                        size_t stripes, const uint8_t* erased, int* status, uint8_t* rewritten, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!erased) return RS_EINVAL;
+    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (c->set && c->m > 0) {
+        rs_ctx* mc = routed(c, data);
+        return mc ? rs_correct_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, status, rewritten,
+                                        stream)
+                  : RS_EINVAL;
+    }
+    // The erasure counts are checked before anything is written or launched.
+    bool degraded = false;
+    const size_t n = static_cast<size_t>(c->n);
+    for (size_t i = 0; i < stripes; ++i) {
+        int e = 0;
+        for (size_t id = 0; id < n; ++id) e += erased[i * n + id] != 0;
+        if (e > c->m) return RS_ENOT_ENOUGH;
+        degraded |= e > 0;
+    }
+    if (!degraded) return rs_correct_stripes(c, data, dss, parity, pss, pitch, len, stripes, status, rewritten, stream);
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (rewritten) std::memset(rewritten, 0, stripes * n);
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return correct_degraded(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, erased, status, rewritten,
+                            static_cast<hipStream_t>(stream));
+}
+
 int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
                       size_t stripes, const rs_shard_update* updates, size_t count, void* stream) {
     if (!c) return RS_EINVAL;
@@ -2894,17 +3201,7 @@ int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity,
     rsmi::ReadPlan plan;
     const int rc = rsmi::plan_reads(c->k, c->n, stripes, erased, span, reads, count, &plan);
     if (rc != RS_OK) return rc;
-    rsmi::ReadArgs a{};
-    a.data = static_cast<const uint8_t*>(data);
-    a.parity = static_cast<const uint8_t*>(parity);
-    a.data_ss = dss;
-    a.parity_ss = pss;
-    a.pitch = pitch;
-    a.ncols16 = static_cast<uint32_t>(span / 16);
-    a.k = static_cast<uint32_t>(c->k);
-    a.m = static_cast<uint32_t>(c->m);
-    a.njobs = static_cast<uint32_t>(plan.jobs.size());
-    a.xcd = c->xcd_split_rec;
+    rsmi::ReadArgs a = read_args(c, data, dss, parity, pss, pitch, len, plan.jobs.size());
     if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
     // launch_copy_pieces: a block per (piece, 4 KiB chunk)
     if (plan.copies.size() * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull) return RS_EINVAL;

@@ -39,6 +39,7 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
+    "rs_verify_degraded", "rs_correct_degraded",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -131,6 +132,8 @@ def _lib() -> ctypes.CDLL:
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
             "rs_update_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
             "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
+            "rs_verify_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
+            "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
             "rs_prepare_patterns": (i32, [vp, i32, vp]),
@@ -297,7 +300,7 @@ class FEC:
 
     def kernel_name(self, which: int = 0) -> str:
         """Kernel serving encode (0), reconstruct (1), verify (2), update
-        (3) or degraded read (4): diagnostics."""
+        (3), degraded read (4) or degraded check (5): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -450,6 +453,39 @@ class FEC:
             _check(rc, "rs_correct_stripes")
         return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
 
+    def verify_degraded(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                        pitch: int, shard_len: int, stripes: int, erased: bytes, first_bad_ptr: int,
+                        stream: int = 0) -> None:
+        """rs_verify_degraded: verify_stripes for stripes with missing shards
+        (erased: stripes * n flags).  first_bad_ptr[s] receives the lowest
+        byte offset at which the present shards of stripe s do not lie on one
+        codeword, or RS_VERIFY_CLEAN; erased slots are never dereferenced.
+        Enqueued on stream."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_verify_degraded(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                         pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p),
+                                         first_bad_ptr or None, stream or None), "rs_verify_degraded")
+
+    def correct_degraded(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                         pitch: int, shard_len: int, stripes: int, erased: bytes, stream: int = 0):
+        """rs_correct_degraded (scrub with missing shards): (status,
+        rewritten) as correct_stripes; located shards are regenerated in
+        place, erased ones are neither touched nor filled in.  Raises only
+        for argument, device or memory errors and for more than m erasures."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        buf = ctypes.c_char_p(bytes(erased))
+        st = (ctypes.c_int * max(stripes, 1))()
+        rw = ctypes.create_string_buffer(max(stripes * self.n, 1))
+        rc = _lib().rs_correct_degraded(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                        pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), st,
+                                        ctypes.cast(rw, ctypes.c_void_p), stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_degraded")
+        return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
+
     def update_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
                        pitch: int, shard_len: int, stripes: int, updates: Sequence[tuple],
                        stream: int = 0) -> None:
@@ -499,7 +535,8 @@ class FEC:
     (STAT_PATTERNS, STAT_EVICTIONS, STAT_BATCHES_IN_PLACE, STAT_BATCHES_STAGED, STAT_LEASES,
      STAT_ENCODES_IN_PLACE, STAT_DECODES_IN_PLACE, STAT_REC_STRIPES_TABLE, STAT_REC_STRIPES_SYNDROME,
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
-     STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED) = range(16)
+     STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
+     STAT_SCRUB_REGENERATED) = range(18)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
