@@ -75,7 +75,9 @@ const char *rs_strerror(int status);
  * reconstruct (which = 1), verify (which = 2), update (which = 3), degraded
  * read (which = 4) or degraded check (which = 5) for this ctx, e.g.
  * "bitslice_k64_m16", "K10_MG4_B256", "verify_K10_MG4_B256",
- * "update_MG4_B256", "read_K10_MG4_B256" or "check_K10_MG4_B256" (no
+ * "update_MG4_B256", "read_K10_MG4_B256" or "check_K10_MG4_B256"; which = 6:
+ * the rs_combine variant that serves a narrow job of this code's shape (nsrc
+ * = k, nout = min(m, 4), or 1 when m is 0), e.g. "combine_MG4_B256" (no
  * reference counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
@@ -322,6 +324,61 @@ int rs_read_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride,
                     size_t shard_len, size_t stripes, const uint8_t *erased,
                     const rs_shard_read *reads, size_t count, void *stream);
 
+/* Caller-chosen GF(2^8) combinations of device buffers: the primitive under
+ * the encode, reconstruct, update and read calls, with the coefficients, the
+ * inputs and the outputs all named by the caller (no reference counterpart).
+ * The ctx's (k, n) plays no part; the ctx supplies the device, the lease and
+ * the stream, as it does for rs_blake2b_device.
+ * jobs: HOST array of `count` jobs, not retained, and neither are the host
+ * arrays a job points to.  Job b computes, for every output row r < nout,
+ *     dst[r]  = sum_c coef[r * nsrc + c] * src[c]     (accumulate == 0)
+ *     dst[r] ^= sum_c coef[r * nsrc + c] * src[c]     (accumulate == 1)
+ * over buffers of `len` bytes, in the engine's field (polynomial 0x11D).
+ * Coefficients 0 and 1 are ordinary values: an all-zero row zeroes its dst
+ * when overwriting and leaves it as it was when accumulating.  All addresses
+ * are DEVICE addresses, 16-byte aligned; round_up(len, 16) bytes of every src
+ * are read and of every dst are written, those past len being unspecified (as
+ * for rs_read_stripes).
+ * Overlap rule: sources may repeat and may overlap each other freely, within
+ * a job and across jobs; a dst range may meet neither a src range of any job
+ * of the call nor another dst range of the call (jobs, and row groups of one
+ * job, run in different blocks, and row groups re-read the sources).  Two
+ * accumulations into one dst therefore take two calls on one stream.
+ * Bytes moved: the kernel codes a job's outputs in row groups of MG = 4, 8 or
+ * 16 rows (the smallest that holds the call's largest nout, 16 beyond; 8 when
+ * the call's largest nsrc is above 199 and its largest nout above 8), each
+ * group reading the sources once, so with G = ceil(nout / MG) a job moves
+ *     (G * nsrc + nout * (1 + accumulate)) * len
+ * bytes: a job of nout <= 16 reads its sources once.
+ * Two uses: a holder of some survivors of a stripe multiplies
+ * them by their columns of a decode row (rs_pattern_rows, rs_pattern_survivors)
+ * into one partial buffer and the owner accumulates the partials; a data
+ * holder turns old and new contents of a shard into the m parity deltas
+ * E[k + r][shard] * (old ^ new) and the parity holder accumulates them with
+ * coefficient 1.
+ * All or nothing: RS_EINVAL for a NULL ctx (before any HIP call), NULL jobs
+ * with count > 0, a job's src, dst or coef NULL, nsrc or nout outside 1..256,
+ * accumulate > 1, reserved != 0, a NULL or misaligned address, a forbidden
+ * overlap, count >= 2^32, a len the stripe calls refuse, tables of 2^32 or
+ * more addresses or coefficients, or more than 2^31 - 1 blocks; nothing is
+ * launched and nothing written then.  count == 0 or len == 0: RS_OK, nothing
+ * launched.
+ * Device sets: the call runs on the member on the device that holds
+ * jobs[0].dst[0], RS_EINVAL if there is none; sources on a peer device are
+ * read where they lie, as rs_reconstruct_spread does.
+ * Enqueued on stream; returns when queued (the small tables are staged
+ * through pinned memory). */
+typedef struct rs_combine_job {
+    const uint64_t *src;   /* HOST array of nsrc DEVICE addresses                */
+    const uint64_t *dst;   /* HOST array of nout DEVICE addresses                */
+    const uint8_t  *coef;  /* HOST, nout x nsrc row-major GF(2^8) coefficients   */
+    uint32_t nsrc;         /* 1..256 */
+    uint32_t nout;         /* 1..256 */
+    uint32_t accumulate;   /* 0: dst[r] = sum_c coef[r][c]*src[c];  1: dst[r] ^= that sum */
+    uint32_t reserved;     /* 0 */
+} rs_combine_job;
+int rs_combine(rs_ctx *ctx, const rs_combine_job *jobs, size_t count, size_t len, void *stream);
+
 /* rs_reconstruct_ptrs: rs_reconstruct_stripes with shards anywhere in
  * device memory.  shard_ptrs is a DEVICE array [stripes][n] of device
  * addresses (16-byte aligned): shard i of stripe s is read (survivor) or
@@ -362,6 +419,8 @@ enum {
     RS_STAT_READ_COPIED = 15,      /* shards rs_read_stripes served by copy            */
     RS_STAT_CHECK_STRIPES = 16,    /* degraded stripes checked by the check kernel (rs_verify_degraded, rs_correct_degraded) */
     RS_STAT_SCRUB_REGENERATED = 17, /* shards regenerated by rs_correct_degraded       */
+    RS_STAT_COMBINE_JOBS = 18,     /* jobs coded by rs_combine                         */
+    RS_STAT_COMBINE_ROWS = 19,     /* output rows written by rs_combine                */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -371,6 +430,13 @@ int64_t rs_stat(const rs_ctx *ctx, int which);
  * t-th erased shard in increasing id order; built on the GPU like every
  * batched pattern.  Synchronises the ctx's device. */
 int rs_pattern_rows(rs_ctx *ctx, const uint8_t *erased, uint8_t *rows, int *count);
+/* The shard ids behind the columns of those rows: ids[c] (k entries) is the
+ * survivor that column c of rs_pattern_rows' rows multiplies for the same
+ * flags -- slot i holds shard i if it is present, otherwise the
+ * highest-numbered remaining parity (Rebuild's choice).  With it a caller
+ * splits a decode row by holder for rs_combine without restating that rule.
+ * RS_ENOT_ENOUGH for more than m erasures.  Host arithmetic only. */
+int rs_pattern_survivors(const rs_ctx *ctx, const uint8_t *erased, int *ids);
 
 /* Precompute (invert and upload) the decode patterns of every erasure set of
  * 1..max_erasures shards (max_erasures <= m), e.g. the 1,470 patterns of

@@ -587,6 +587,143 @@ __global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
     }
 }
 
+// Caller-chosen combinations (rs_kernels.hpp CombArgs): rs_update_kernel's
+// block decomposition with everything a job's own -- nsrc sources as the
+// runtime "k", nout outputs cut into row groups of MG, the coefficient rows
+// read from the job's slice of the coefficient table.  In accumulate mode the
+// accumulators start as the stored destination columns and go back where they
+// came from (as the update's parity); in overwrite mode they start at zero
+// and the destinations are never read.
+// LDS: [nsrc][MG/4][20] table dwords | nsrc source pointers.
+template <int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG % 4 == 0, "whole sub-steps");
+    constexpr int TG = MG / kRowsPerStep;  // sub-steps per source
+    // Sources whose loads are in flight, next to the MG stored columns of an
+    // accumulating job: 4, the update kernel's depth (two shards, old and
+    // new).  8 cost 138 VGPRs against 120 for MG 4 -- three waves per SIMD
+    // where the update kernel runs four.
+    constexpr int JB = 4;
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const CombineJob job = a.jobs[b / a.chunks];
+    const int nsrc = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.nsrc));
+    const int nout = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.nout));
+    const bool accumulate = __builtin_amdgcn_readfirstlane(job.accumulate) != 0;
+    const int row0 = static_cast<int>(grp) * MG;
+    if (row0 >= nout) return;  // whole block: uniform
+    const int eg = min(MG, nout - row0);
+    const uint64_t* sa = a.addrs + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.addr));
+    const uint64_t* da = sa + nsrc + row0;
+    const uint8_t* cf = a.coef + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.coef)) +
+                        static_cast<size_t>(row0) * nsrc;
+
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + nsrc * TG * kStepWords);
+    for (int i = threadIdx.x; i < nsrc; i += BT) sptr[i] = reinterpret_cast<uint8_t*>(sa[i]);
+    // Destinations of this group's rows; rows past eg have none.
+    uint8_t* dp[MG];
+#pragma unroll
+    for (int r = 0; r < MG; ++r) dp[r] = r < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(da[r])) : nullptr;
+
+    const uint32_t last = a.ncols16 - 1;
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    uint32_t acc[TG][kRowsPerStep][4];
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                uint4 p = make_uint4(0u, 0u, 0u, 0u);
+                if (accumulate && g * kRowsPerStep + r < eg) p = gload16<NT>(dp[g * kRowsPerStep + r] + at);
+                acc[g][r][0] = p.x;
+                acc[g][r][1] = p.y;
+                acc[g][r][2] = p.z;
+                acc[g][r][3] = p.w;
+            }
+    };
+    // The first iteration's loads -- the stored columns and the first JB
+    // sources, their addresses taken straight from the address table -- go
+    // out before the table build; with one iteration per block and nsrc <= JB
+    // that is the whole data path.
+    load_stored(off0);
+    uint4 x[JB];
+#pragma unroll
+    for (int q = 0; q < JB; ++q) {
+        if (q >= nsrc) break;
+        x[q] = gload16<NT>(uniform_ptr(reinterpret_cast<uint8_t*>(sa[q])) + off0);
+    }
+    // Split tables: sub-step (c, g) holds coef[row0 + 4g .. + 3][c].
+    for (int idx = threadIdx.x; idx < nsrc * MG; idx += BT) {
+        const int c = idx / MG, t = idx - c * MG;
+        const uint32_t v = (t < eg) ? cf[static_cast<size_t>(t) * nsrc + c] : 0u;
+        build_tables(v, &tw[(c * TG + t / kRowsPerStep) * kStepWords + (t % kRowsPerStep) * 5]);
+    }
+    __syncthreads();
+
+    [[maybe_unused]] const int tg_used = (eg + kRowsPerStep - 1) / kRowsPerStep;
+    bool preloaded = true;
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;
+        // Tail lanes re-read the last column and store nothing: the lane that
+        // owns that column may have written it already.
+        const uint32_t off = (ok ? col : last) * 16u;
+        if (!preloaded) load_stored(off);
+        for (int jb = 0; jb < nsrc; jb += JB) {
+            if (!preloaded) {
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (jb + q >= nsrc) break;
+                    x[q] = gload16<NT>(uniform_ptr(sptr[jb + q]) + off);
+                }
+            }
+            preloaded = false;
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb * TG) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (jb + q >= nsrc) break;
+#pragma unroll
+                for (int g = 0; g < TG; ++g) {
+                    const int step = (jb + q) * TG + g;
+                    const bool more = (g + 1 < TG) || (q + 1 < JB && jb + q + 1 < nsrc);
+                    if (more) load_step(lds4 + static_cast<size_t>(step + 1) * (kStepWords / 4), TB);
+                    // Row groups of 4 multiply only the group's eg rows (a
+                    // job of one output pays for one); wider ones whole
+                    // sub-steps, as the update kernel.
+                    if constexpr (TG == 1) {
+                        if (eg == kRowsPerStep) mac_step(acc[g], x[q], TA);
+                        else mac_step_rows(acc[g], x[q], TA, eg);
+                    } else if (g < tg_used) {
+                        mac_step(acc[g], x[q], TA);
+                    }
+                    step_fence(acc[g]);
+#pragma unroll
+                    for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                const int t = g * kRowsPerStep + r;
+                if (t >= eg) break;
+                if (ok) gstore16<NT>(dp[t] + off, make_uint4(acc[g][r][0], acc[g][r][1], acc[g][r][2], acc[g][r][3]));
+            }
+    }
+}
+
 // Degraded read (rs_kernels.hpp ReadArgs): the split-table matmul_block with
 // the rows and the outputs taken from the job's entry table instead of the
 // pattern.  Row t of the block's group is row entries[first + row0 + t].row of
@@ -1125,6 +1262,28 @@ const UpdateVariant& pick_update(int m, uint32_t max_j) {
     return update_lds(v.MG, max_j) <= kUpdateLdsMax ? v : kUpdate[1];
 }
 
+// Combine variants: the update kernel's row groups, chosen from the call's
+// largest nout, so that a job of up to 16 outputs reads its sources once.
+struct CombineVariant {
+    int MG;
+    const char* name;
+    void (*fn)(CombArgs);
+};
+#define RS_COMBINE(MG) {MG, "combine_MG" #MG "_B256", rs_combine_kernel<MG, kBlock, true>}
+const CombineVariant kCombine[] = {RS_COMBINE(4), RS_COMBINE(8), RS_COMBINE(16)};
+#undef RS_COMBINE
+
+size_t combine_lds(int mg, uint32_t max_nsrc) {
+    return static_cast<size_t>(max_nsrc) * (mg / kRowsPerStep) * kStepWords * 4 + static_cast<size_t>(max_nsrc) * sizeof(void*);
+}
+
+// A job of more than 199 sources does not fit the LDS with row groups of 16
+// (328 bytes per source); it takes row groups of 8.
+const CombineVariant& pick_combine(uint32_t max_nsrc, uint32_t max_nout) {
+    const CombineVariant& v = kCombine[max_nout <= 4 ? 0 : max_nout <= 8 ? 1 : 2];
+    return combine_lds(v.MG, max_nsrc) <= kUpdateLdsMax ? v : kCombine[1];
+}
+
 // Read variants: always the split-table kernel with row groups of 4 wanted
 // rows, also for the codes whose reconstruct runs the syndrome network.
 struct ReadVariant {
@@ -1228,6 +1387,40 @@ hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream) {
     for (const UpdateVariant& u : kUpdate)
         if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
     const size_t lds = update_lds(static_cast<int>(a.mg), max_j);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
+
+const char* combine_variant_name(int nsrc, int nout) {
+    return pick_combine(static_cast<uint32_t>(nsrc), static_cast<uint32_t>(nout)).name;
+}
+
+bool plan_combine_launch(CombArgs* a, uint32_t max_nsrc, uint32_t max_nout) {
+    const CombineVariant& v = pick_combine(max_nsrc, max_nout);
+    const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
+    static const uint32_t iters_cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    a->iters = std::min<uint32_t>(iters_cap, std::max<uint32_t>(total_it, 1));
+    a->chunks = (total_it + a->iters - 1) / a->iters;
+    a->mg = static_cast<uint32_t>(v.MG);
+    a->groups = (max_nout + a->mg - 1) / a->mg;
+    const uint64_t blocks = static_cast<uint64_t>(a->njobs) * a->chunks * a->groups;
+    if (blocks > 0x7FFFFFFFull) return false;
+    if (a->xcd == ~0u) a->xcd = a->chunks * a->groups;  // a job per XCD region
+    return true;
+}
+
+hipError_t launch_combine(const CombArgs& a, uint32_t max_nsrc, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0 || max_nsrc == 0) return hipSuccess;
+    const CombineVariant* v = nullptr;
+    for (const CombineVariant& u : kCombine)
+        if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
+    const size_t lds = combine_lds(static_cast<int>(a.mg), max_nsrc);
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);

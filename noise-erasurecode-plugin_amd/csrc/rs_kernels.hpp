@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "combine_plan.hpp"
 #include "read_plan.hpp"
 #include "update_plan.hpp"
 
@@ -150,6 +151,29 @@ struct UpdArgs {
 bool plan_update(UpdArgs* a, uint32_t max_j);
 hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream);  // a: planned
 const char* update_variant_name(int m);  // "update_MG4_B256" etc.
+
+// Caller-chosen combinations (rs_combine): job b of `jobs` (combine_plan.hpp)
+// multiplies its nsrc source buffers by its nout x nsrc coefficients and
+// stores the nout sums at its destinations, or XORs them in (accumulate):
+//     *dst[r] (^)= sum_c coef[job.coef + r * nsrc + c] * *src[c]
+// A block is {job, 4 KiB column chunk, row group of MG outputs}; a job with
+// fewer row groups than the call's widest leaves its surplus blocks idle.
+struct CombArgs {
+    const CombineJob* jobs;  // [njobs] (device)
+    const uint64_t* addrs;   // (device) a job's sources, then its destinations
+    const uint8_t* coef;     // (device)
+    uint32_t ncols16;        // 16-byte columns per buffer
+    uint32_t njobs;
+    uint32_t xcd;            // XCD-aware block order, as MatArgs
+    // Filled in by plan_combine_launch:
+    uint32_t chunks, groups, iters;
+    uint32_t mg;  // row-group size of the variant chosen
+};
+// Chooses the variant for the call's largest nsrc and nout and fills in the
+// launch plan; false when the grid would exceed 2^31 - 1 blocks.
+bool plan_combine_launch(CombArgs* a, uint32_t max_nsrc, uint32_t max_nout);
+hipError_t launch_combine(const CombArgs& a, uint32_t max_nsrc, hipStream_t stream);  // a: planned
+const char* combine_variant_name(int nsrc, int nout);  // "combine_MG4_B256" etc.
 
 // Degraded read (rs_read_stripes): job b = {stripe, first, j} of `jobs`, whose
 // stripe uses decode pattern pats[b] of the ctx's pattern cache, regenerates

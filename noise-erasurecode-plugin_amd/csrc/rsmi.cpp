@@ -30,6 +30,7 @@
 #include "bitslice.hpp"
 #include "blake2b.hpp"
 #include "check_plan.hpp"
+#include "combine_plan.hpp"
 #include "device_set.hpp"
 #include "gf256.hpp"
 #include "gf_invert.hpp"
@@ -367,6 +368,7 @@ struct rs_ctx {
     std::atomic<int64_t> update_stripes{0}, update_copy_commits{0};      // rs_update_stripes (rs_stat)
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
+    std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1234,6 +1236,40 @@ int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, si
     if (e == hipSuccess) {
         c->update_stripes += static_cast<int64_t>(njobs);
         if (copy_commit) ++c->update_copy_commits;
+    }
+    return hip_status(e);
+}
+
+// -------------------------------------------------------------- combine ----
+// rs_combine on stream s with lease L: the planned job, address and
+// coefficient tables go through the lease's pinned staging into its device
+// buffer in one upload, as update_stripes' tables do; then the combine kernel.
+int combine(rs_ctx* c, Lease& L, const rsmi::CombinePlan& plan, rsmi::CombArgs a, hipStream_t s) {
+    const size_t njobs = plan.jobs.size();
+    const size_t addr_off = njobs * sizeof(rsmi::CombineJob);
+    const size_t coef_off = addr_off + plan.addrs.size() * sizeof(uint64_t);
+    const size_t bytes = coef_off + plan.coef.size();
+    L.begin(s);  // the table buffer's previous readers
+    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+    std::memcpy(hb, plan.jobs.data(), addr_off);
+    std::memcpy(hb + addr_off, plan.addrs.data(), coef_off - addr_off);
+    std::memcpy(hb + coef_off, plan.coef.data(), plan.coef.size());
+    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
+    L.st_stripe.release_after(s);
+    if (e != hipSuccess) {
+        L.end(s);
+        return RS_EDEVICE;
+    }
+    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    a.jobs = reinterpret_cast<const rsmi::CombineJob*>(db);
+    a.addrs = reinterpret_cast<const uint64_t*>(db + addr_off);
+    a.coef = db + coef_off;
+    e = rsmi::launch_combine(a, plan.max_nsrc, s);
+    L.end(s);
+    if (e == hipSuccess) {
+        c->combine_jobs += static_cast<int64_t>(njobs);
+        c->combine_rows += static_cast<int64_t>(plan.rows);
     }
     return hip_status(e);
 }
@@ -2863,6 +2899,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 3) return rsmi::update_variant_name(c->m);
     if (which == 4) return rsmi::read_variant_name(c->k);
     if (which == 5) return rsmi::check_variant_name(c->k);
+    if (which == 6) return rsmi::combine_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2919,6 +2956,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_READ_COPIED: return c->read_copied.load();
         case RS_STAT_CHECK_STRIPES: return c->check_stripes.load();
         case RS_STAT_SCRUB_REGENERATED: return c->scrub_regenerated.load();
+        case RS_STAT_COMBINE_JOBS: return c->combine_jobs.load();
+        case RS_STAT_COMBINE_ROWS: return c->combine_rows.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -2952,6 +2991,14 @@ int rs_pattern_rows(rs_ctx* c, const uint8_t* erased, uint8_t* rows, int* count)
         return RS_EDEVICE;
     *count = static_cast<int>(c->h_cnt[id]);
     return pattern_status(c, id, 1, s);  // synchronises s
+}
+
+int rs_pattern_survivors(const rs_ctx* c, const uint8_t* erased, int* ids) {
+    if (!c || !erased || !ids) return RS_EINVAL;
+    if (c->set) return rs_pattern_survivors(rsmi::set_member(c->set, 0), erased, ids);
+    uint8_t present[256];
+    for (int i = 0; i < c->n; ++i) present[i] = erased[i] ? 0 : 1;
+    return rsmi::choose_survivors_into(present, c->k, c->n, ids) == c->k ? RS_OK : RS_ENOT_ENOUGH;
 }
 
 int rs_prepare_patterns(rs_ctx* c, int max_e, void* stream) {
@@ -3210,6 +3257,28 @@ int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity,
     LeaseGuard lg(c);
     if (!lg.L) return RS_ENOMEM;
     return read_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, a, static_cast<hipStream_t>(stream));
+}
+
+int rs_combine(rs_ctx* c, const rs_combine_job* jobs, size_t count, size_t len, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || len == 0) return RS_OK;
+    rsmi::CombinePlan plan;
+    const int rc = rsmi::plan_combine(jobs, count, len, &plan);
+    if (rc != RS_OK) return rc;
+    if (c->set) {  // the member on the device of the first destination
+        c = routed(c, reinterpret_cast<const void*>(static_cast<uintptr_t>(plan.addrs[plan.jobs[0].nsrc])));
+        if (!c) return RS_EINVAL;
+    }
+    rsmi::CombArgs a{};
+    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
+    a.njobs = static_cast<uint32_t>(plan.jobs.size());
+    a.xcd = c->xcd_update;
+    if (!rsmi::plan_combine_launch(&a, plan.max_nsrc, plan.max_nout)) return RS_EINVAL;
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return combine(c, *lg.L, plan, a, static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

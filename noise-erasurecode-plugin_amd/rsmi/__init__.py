@@ -39,7 +39,7 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
-    "rs_verify_degraded", "rs_correct_degraded",
+    "rs_verify_degraded", "rs_correct_degraded", "rs_combine", "rs_pattern_survivors",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -82,6 +82,34 @@ class ShardRead(ctypes.Structure):
 def shard_reads(reads: Sequence[tuple]) -> ctypes.Array:
     """The rs_shard_read table of (stripe, shard, dst_ptr) tuples."""
     return (ShardRead * len(reads))(*[ShardRead(s, i, 0, p) for s, i, p in reads])
+
+
+class CombineJob(ctypes.Structure):
+    """rs_combine_job (include/rsmi.h): nout combinations of nsrc buffers."""
+
+    _fields_ = [("src", ctypes.POINTER(ctypes.c_uint64)), ("dst", ctypes.POINTER(ctypes.c_uint64)),
+                ("coef", ctypes.POINTER(ctypes.c_uint8)), ("nsrc", ctypes.c_uint32), ("nout", ctypes.c_uint32),
+                ("accumulate", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def combine_jobs(jobs: Sequence[tuple]) -> ctypes.Array:
+    """The rs_combine_job table of (src_ptrs, dst_ptrs, coef, accumulate)
+    tuples: coef holds len(dst_ptrs) * len(src_ptrs) coefficient bytes, row
+    by row.  The table keeps the host arrays its jobs point to alive."""
+    arr = (CombineJob * max(len(jobs), 1))()
+    keep = []
+    for job, (src, dst, coef, accumulate) in zip(arr, jobs):
+        coef = bytes(coef)
+        if len(coef) != len(src) * len(dst):
+            raise RSError(RS_EINVAL, "coef must hold nout*nsrc coefficients")
+        hs, hd = (ctypes.c_uint64 * len(src))(*src), (ctypes.c_uint64 * len(dst))(*dst)
+        hc = (ctypes.c_uint8 * max(len(coef), 1)).from_buffer_copy(coef or b"\0")
+        keep.append((hs, hd, hc))
+        job.src, job.dst, job.coef = hs, hd, hc
+        job.nsrc, job.nout, job.accumulate = len(src), len(dst), int(accumulate)
+    arr._keep = keep
+    arr._count = len(jobs)
+    return arr
 
 
 class RSError(Exception):
@@ -134,6 +162,8 @@ def _lib() -> ctypes.CDLL:
             "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_verify_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
+            "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
+            "rs_pattern_survivors": (i32, [vp, vp, ctypes.POINTER(i32)]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
             "rs_prepare_patterns": (i32, [vp, i32, vp]),
@@ -516,6 +546,26 @@ class FEC:
                                       pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), arr,
                                       len(reads), stream or None), "rs_read_stripes")
 
+    def combine(self, jobs: Sequence[tuple], length: int, stream: int = 0) -> None:
+        """rs_combine: jobs is a sequence of (src_ptrs, dst_ptrs, coef,
+        accumulate); every job multiplies its source buffers (device
+        addresses, `length` bytes each) by its nout x nsrc coefficient bytes
+        and stores the nout sums at dst_ptrs, or XORs them in when accumulate
+        is set.  A caller that repeats a large list passes the table
+        combine_jobs() built from it instead.  Enqueued on stream."""
+        arr = jobs if isinstance(jobs, ctypes.Array) else combine_jobs(jobs)
+        _check(_lib().rs_combine(self._h, arr, arr._count, length, stream or None), "rs_combine")
+
+    def pattern_survivors(self, erased: bytes) -> List[int]:
+        """The shard id behind each of the k columns of pattern_rows(erased)."""
+        if len(erased) != self.n:
+            raise RSError(RS_EINVAL, "erased must hold n flags")
+        ids = (ctypes.c_int * self.k)()
+        flags = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_pattern_survivors(self._h, ctypes.cast(flags, ctypes.c_void_p), ids),
+               "rs_pattern_survivors")
+        return list(ids)
+
     def reconstruct_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
                          stream: int = 0) -> None:
         """rs_reconstruct_ptrs: shard i of stripe s at the device address in
@@ -536,7 +586,7 @@ class FEC:
      STAT_ENCODES_IN_PLACE, STAT_DECODES_IN_PLACE, STAT_REC_STRIPES_TABLE, STAT_REC_STRIPES_SYNDROME,
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
-     STAT_SCRUB_REGENERATED) = range(18)
+     STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS) = range(20)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
