@@ -77,7 +77,8 @@ const char *rs_strerror(int status);
  * "bitslice_k64_m16", "K10_MG4_B256", "verify_K10_MG4_B256",
  * "update_MG4_B256", "read_K10_MG4_B256" or "check_K10_MG4_B256"; which = 6:
  * the rs_combine variant that serves a narrow job of this code's shape (nsrc
- * = k, nout = min(m, 4), or 1 when m is 0), e.g. "combine_MG4_B256" (no
+ * = k, nout = min(m, 4), or 1 when m is 0), e.g. "combine_MG4_B256"; which =
+ * 7: the rs_update_degraded variant, e.g. "update_degraded_MG4_B256" (no
  * reference counterpart). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
@@ -278,6 +279,63 @@ int rs_update_stripes(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *
                       size_t stripes, const rs_shard_update *updates, size_t count,
                       void *stream);
 
+/* In-place parity update of stripes with missing shards: rs_update_stripes
+ * for a store that has lost shards and must go on accepting writes until the
+ * repair has run.  Layout, alignment and `updates` as rs_update_stripes;
+ * erased is a HOST array of stripes * n flags as for rs_reconstruct_stripes,
+ * not retained; only the flags of listed stripes are examined.
+ * For a listed stripe with erased set X (e ids, e_par of them parity) and
+ * changed data shards U = U_p (present) + U_x (erased), every PRESENT parity
+ * shard r becomes
+ *     parity[r] ^= sum_{c in U} E[k + r][c] * (old_c ^ new_c).
+ * For c in U_p old_c is read from the shard's slot, which then takes the new
+ * contents.  For c in U_x old_c is regenerated from the k survivors Rebuild
+ * chooses for X, read in their state before the call, with the decode row of
+ * the ctx's pattern cache that rs_read_stripes would use (the row of c's rank
+ * among the erased ids); the slot of c is NOT written: its new contents live
+ * in the parity alone, and a later rs_reconstruct_stripes with the same flags
+ * produces them.  The slots of erased shards, data or parity, changed or not,
+ * are never dereferenced, for reading or writing.
+ * Trust: the stored shards are patched, not recomputed.  A stripe whose
+ * present shards lay on one codeword before the call (rs_verify_degraded)
+ * still does after it.  A wrong byte in a present parity shard that is not
+ * one of the survivors stays wrong by the same XOR difference, as for
+ * rs_update_stripes; the survivors are trusted as the parity is: a wrong byte
+ * in one of them goes into the regenerated old_c and from there into every
+ * present parity shard.
+ * Bytes moved per stripe with j changed shards (j_p of them present), S =
+ * shard_len: with U_x empty (3j + 2(m - e_par)) * S; with U_x non-empty, on
+ * the fused path, (k + j + j_p + 2(m - e_par)) * S in one pass and without
+ * scratch -- the survivors are read instead of the old contents; that pass does
+ * (m - e_par) * (k + j) multiplies per column, every source into every present
+ * parity row, and is compute-bound for wide codes.  Where only
+ * the changed shard is missing and the other k - 1 data shards are present,
+ * copying nothing and re-encoding from the new contents costs (k + m - e_par)
+ * * S and is cheaper; the caller chooses.
+ * The fused path serves a call unless m > 16 or the tables of its widest job
+ * (k + j sources) pass the 64 KiB of LDS; such a call takes the SLOW path: the
+ * old contents of its erased changed shards are regenerated by the degraded
+ * read's kernel into a scratch buffer of the ctx's, round_up(shard_len, 16)
+ * bytes for each of them, every stripe is then patched from (old, new) pairs,
+ * and the new contents of present shards are copied in by a pass behind that.
+ * A slice update works as documented for rs_update_stripes.
+ * All or nothing: everything rs_update_stripes refuses, with its codes, and
+ * RS_EINVAL for NULL erased; RS_ENOT_ENOUGH for a listed stripe that has an
+ * erased changed shard and more than m erasures (defects of the list are
+ * reported first, the flags are looked at last); RS_ENOMEM if the slow path's
+ * scratch cannot be had; nothing is launched or written then.  A listed stripe
+ * with more than m erasures whose changed shards are all present is served:
+ * its patch needs no decode.  count == 0, stripes == 0 or shard_len == 0:
+ * RS_OK, nothing launched.  With m == 0 present changed shards are
+ * overwritten and an erased one is RS_ENOT_ENOUGH.  If no listed stripe has a
+ * flag set the call is rs_update_stripes.
+ * Enqueued on stream; returns when queued (the small job tables are staged
+ * through pinned memory). */
+int rs_update_degraded(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                       size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                       size_t stripes, const uint8_t *erased,
+                       const rs_shard_update *updates, size_t count, void *stream);
+
 /* Degraded read: fetch listed shards of stripes while some of their shards
  * are missing, without repairing anything.  Layout and alignment rules as
  * rs_encode_stripes; erased is a HOST array of stripes * n flags as for
@@ -421,6 +479,8 @@ enum {
     RS_STAT_SCRUB_REGENERATED = 17, /* shards regenerated by rs_correct_degraded       */
     RS_STAT_COMBINE_JOBS = 18,     /* jobs coded by rs_combine                         */
     RS_STAT_COMBINE_ROWS = 19,     /* output rows written by rs_combine                */
+    RS_STAT_UPDATE_DEGRADED = 20,  /* stripes patched by the rs_update_degraded kernel */
+    RS_STAT_UPDATE_ABSORBED = 21,  /* erased changed shards rs_update_degraded took into the parity only */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -531,7 +591,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
- *    rs_verify_degraded, rs_correct_degraded, rs_reconstruct_ptrs,
+ *    rs_verify_degraded, rs_correct_degraded, rs_update_degraded, rs_reconstruct_ptrs,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

@@ -24,6 +24,15 @@ __device__ __forceinline__ uint32_t xtime(uint32_t a) {
     return a ^ ((a & 0x100u) ? 0x11Du : 0u);
 }
 
+// Scalar product a * b of two field elements from the exp / log tables the
+// context uploads behind its encode matrix (exp: 512 entries, so the sum of
+// two logs needs no reduction; log: 256).  For coefficients a block composes
+// itself ahead of its table build.
+__device__ __forceinline__ uint32_t gf_mul(const uint8_t* gf_exp, const uint8_t* gf_log, uint32_t a, uint32_t b) {
+    if (a == 0u || b == 0u) return 0u;
+    return gf_exp[static_cast<uint32_t>(gf_log[a]) + gf_log[b]];
+}
+
 // Split-table words of coefficient c (host twin: gf256.cpp coef_tables).
 __device__ inline void build_tables(uint32_t c, uint32_t* w) {
     uint32_t p[8];

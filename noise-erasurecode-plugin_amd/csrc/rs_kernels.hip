@@ -724,6 +724,231 @@ __global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
     }
 }
 
+// In-place parity update of stripes with missing shards (rs_kernels.hpp
+// DegArgs): rs_update_kernel's block decomposition and accumulators -- the
+// stored columns of the job's PRESENT parity rows, which go back where they
+// came from -- over rs_combine_kernel's source loop.  A source is up to two
+// loads, XORed, and an optional commit address:
+//   pair form    source c = (new_c, old_c), coefficient E[k + r][c]; old_c is
+//                the shard's slot, or the entry's `old` buffer;
+//   decode form  sources 0 .. k - 1 are the survivors of the job's pattern,
+//                k .. k + j - 1 the new buffers.  With D the pattern's decode
+//                rows, old_c = sum_i D[rank_c][i] * survivor_i for an erased
+//                changed shard c, so the patch of row r is
+//                    sum_i (sum_{c in U_x} E[k+r][c] * D[rank_c][i]) * survivor_i
+//                  ^ sum_{c' in U_p} E[k+r][c'] * survivor_c'   (a present data
+//                    shard is the survivor of its own slot)
+//                  ^ sum_{c in U} E[k+r][c] * new_c,
+//                and the block composes those coefficients in its table build
+//                (gfd::gf_mul).  No scratch, and no slot of an erased shard is
+//                ever addressed: the survivors are present by construction,
+//                the rows are the present ones, and only present changed
+//                shards have a commit address.
+// In place: in the decode form a parity survivor is a source AND an output,
+// and a present changed shard is a source and is overwritten.  That is safe
+// only because ONE block owns every read and write of a column of a stripe --
+// hence one row group (groups == 1) -- and, lane by lane, it reads all of
+// them in program order before it stores any: the accumulators and every
+// survivor's column are loaded before the first commit (the new buffers
+// follow the survivors in the source order) and the parity goes out last.
+// Tail lanes re-read the last column and store nothing, as in the update
+// kernel, and nothing is prefetched for the next iteration but other columns.
+// The pair form has no such source, so it may run several row groups; then
+// commit is 0 and the caller copies the new contents in behind the kernel.
+// LDS: [nsrc][MG/4][20] table dwords | nsrc x {load, second load or 0, commit or 0}.
+template <int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_update_degraded_kernel(DegArgs a) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG % 4 == 0, "whole sub-steps");
+    constexpr int TG = MG / kRowsPerStep;  // sub-steps per source
+    // Sources whose loads are in flight, next to the MG parity loads: 4 as in
+    // the combine kernel -- a pair-form job of two changed shards has all its
+    // loads out at once, as in the update kernel.
+    constexpr int JB = 4;
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const DegJob job = a.jobs[b / a.chunks];
+    const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe))) |
+                       (static_cast<uint64_t>(static_cast<uint32_t>(
+                            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe >> 32))))
+                        << 32);
+    const DegEntry* ent = a.entries + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.first));
+    const int j = __builtin_amdgcn_readfirstlane(job.j);
+    const int jp = j - static_cast<int>(__builtin_amdgcn_readfirstlane(job.jx));  // present entries come first
+    const int nrows = __builtin_amdgcn_readfirstlane(job.nrows);
+    const uint32_t pat = __builtin_amdgcn_readfirstlane(job.pat);
+    const bool decode = pat != kDegNoPattern;
+    const int k = static_cast<int>(a.k);
+    const int nsrc = decode ? k + j : j;
+    const int row0 = static_cast<int>(grp) * MG;
+    // A job with fewer present rows than the call's row groups cover leaves
+    // its surplus blocks idle; the first block stays, with no rows at all if
+    // need be: it commits the data.
+    if (grp > 0 && row0 >= nrows) return;  // whole block: uniform
+    const int eg = max(0, min(MG, nrows - row0));
+    const uint32_t* rows = a.rows + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.row_first)) + row0;
+    const uint32_t* srcid = decode ? a.src + static_cast<size_t>(pat) * k : nullptr;
+    const uint8_t* drow = decode ? a.coef + static_cast<size_t>(pat) * a.m * k : nullptr;
+    uint8_t* dbase = a.data + s * a.data_ss;
+    uint8_t* pbase = a.parity + s * a.parity_ss;
+
+    // Source i: what to load (l0, and l1 or null) and where the block commits
+    // l0's column afterwards (cm or null).
+    auto source = [&](int i, uint8_t*& l0, uint8_t*& l1, uint8_t*& cm) {
+        l1 = nullptr;
+        cm = nullptr;
+        if (decode && i < k) {
+            const uint32_t id = srcid[i];
+            l0 = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                          : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+            return;
+        }
+        const DegEntry e = ent[decode ? i - k : i];
+        uint8_t* slot = dbase + static_cast<uint64_t>(e.shard) * a.pitch;
+        l0 = reinterpret_cast<uint8_t*>(e.src);
+        if (!decode) l1 = e.old ? reinterpret_cast<uint8_t*>(e.old) : slot;
+        if (a.commit && e.rank == kDegPresent) cm = slot;
+    };
+
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** sp = reinterpret_cast<uint8_t**>(tw + nsrc * TG * kStepWords);
+    for (int i = threadIdx.x; i < nsrc; i += BT) source(i, sp[3 * i], sp[3 * i + 1], sp[3 * i + 2]);
+    // Present parity rows of this group; rows past eg are never dereferenced.
+    uint8_t* pp[MG];
+#pragma unroll
+    for (int r = 0; r < MG; ++r)
+        pp[r] = r < eg ? uniform_ptr(pbase + static_cast<uint64_t>(rows[r]) * a.pitch) : nullptr;
+
+    const uint32_t last = a.ncols16 - 1;
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    uint32_t acc[TG][kRowsPerStep][4];
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                uint4 p = make_uint4(0u, 0u, 0u, 0u);
+                if (g * kRowsPerStep + r < eg) p = gload16<NT>(pp[g * kRowsPerStep + r] + at);
+                acc[g][r][0] = p.x;
+                acc[g][r][1] = p.y;
+                acc[g][r][2] = p.z;
+                acc[g][r][3] = p.w;
+            }
+    };
+    // The first iteration's loads -- the stored parity columns and the first
+    // JB sources, their addresses taken straight from the tables -- go out
+    // before the table build, as in the update kernel.
+    load_stored(off0);
+    uint4 x0[JB], x1[JB];
+#pragma unroll
+    for (int q = 0; q < JB; ++q) {
+        if (q >= nsrc) break;
+        uint8_t *l0, *l1, *cm;
+        source(q, l0, l1, cm);
+        l1 = uniform_ptr(l1);
+        x0[q] = gload16<NT>(uniform_ptr(l0) + off0);
+        x1[q] = make_uint4(0u, 0u, 0u, 0u);
+        if (l1) x1[q] = gload16<NT>(l1 + off0);
+    }
+    // Split tables: sub-step (c, g) holds source c's coefficients for rows
+    // rows[4g .. 4g + 3] of the group.
+    const uint8_t* gf_exp = a.enc + static_cast<size_t>(a.k + a.m) * a.k;
+    const uint8_t* gf_log = gf_exp + 512;
+    for (int idx = threadIdx.x; idx < nsrc * MG; idx += BT) {
+        const int c = idx / MG, t = idx - c * MG;
+        uint32_t cf = 0u;
+        if (t < eg) {
+            const uint8_t* er = a.enc + static_cast<size_t>(a.k + rows[t]) * a.k;  // E[k + r][.]
+            if (!decode) {
+                cf = er[ent[c].shard];
+            } else if (c >= k) {
+                cf = er[ent[c - k].shard];
+            } else {
+                for (int x = jp; x < j; ++x)
+                    cf ^= gfd::gf_mul(gf_exp, gf_log, er[ent[x].shard], drow[static_cast<size_t>(ent[x].rank) * k + c]);
+                // A present data shard is the survivor of its own slot: if it
+                // changes, its old contents are this source.
+                const uint32_t id = srcid[c];
+                if (id < a.k)
+                    for (int x = 0; x < jp; ++x)
+                        if (ent[x].shard == id) cf ^= er[id];
+            }
+        }
+        build_tables(cf, &tw[(c * TG + t / kRowsPerStep) * kStepWords + (t % kRowsPerStep) * 5]);
+    }
+    __syncthreads();
+
+    [[maybe_unused]] const int tg_used = (eg + kRowsPerStep - 1) / kRowsPerStep;
+    bool preloaded = true;
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;
+        // Tail lanes re-read the last column and store nothing: the lane that
+        // owns that column may have patched it already.
+        const uint32_t off = (ok ? col : last) * 16u;
+        if (!preloaded) load_stored(off);
+        for (int jb = 0; jb < nsrc; jb += JB) {
+            if (!preloaded) {
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (jb + q >= nsrc) break;
+                    uint8_t* l1 = uniform_ptr(sp[3 * (jb + q) + 1]);
+                    x0[q] = gload16<NT>(uniform_ptr(sp[3 * (jb + q)]) + off);
+                    x1[q] = make_uint4(0u, 0u, 0u, 0u);
+                    if (l1) x1[q] = gload16<NT>(l1 + off);
+                }
+            }
+            preloaded = false;
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb * TG) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (jb + q >= nsrc) break;
+                const uint4 x = make_uint4(x0[q].x ^ x1[q].x, x0[q].y ^ x1[q].y, x0[q].z ^ x1[q].z, x0[q].w ^ x1[q].w);
+#pragma unroll
+                for (int g = 0; g < TG; ++g) {
+                    const int step = (jb + q) * TG + g;
+                    const bool more = (g + 1 < TG) || (q + 1 < JB && jb + q + 1 < nsrc);
+                    if (more) load_step(lds4 + static_cast<size_t>(step + 1) * (kStepWords / 4), TB);
+                    // Row groups of 4 multiply only the present rows (a stripe
+                    // that has lost three of four parity shards pays for
+                    // one); wider ones whole sub-steps, as the combine kernel.
+                    if constexpr (TG == 1) {
+                        if (eg == kRowsPerStep) mac_step(acc[g], x, TA);
+                        else mac_step_rows(acc[g], x, TA, eg);
+                    } else if (g < tg_used) {
+                        mac_step(acc[g], x, TA);
+                    }
+                    step_fence(acc[g]);
+#pragma unroll
+                    for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+                }
+                // Commit: every load of this column that reads the shard's
+                // old contents -- its own pair, or the survivors, all of them
+                // ahead of the new buffers -- has been issued by this lane.
+                uint8_t* cm = uniform_ptr(sp[3 * (jb + q) + 2]);
+                if (cm && ok) gstore16<NT>(cm + off, x0[q]);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < TG; ++g)
+#pragma unroll
+            for (int r = 0; r < kRowsPerStep; ++r) {
+                const int t = g * kRowsPerStep + r;
+                if (t >= eg) break;
+                if (ok) gstore16<NT>(pp[t] + off, make_uint4(acc[g][r][0], acc[g][r][1], acc[g][r][2], acc[g][r][3]));
+            }
+    }
+}
+
 // Degraded read (rs_kernels.hpp ReadArgs): the split-table matmul_block with
 // the rows and the outputs taken from the job's entry table instead of the
 // pattern.  Row t of the block's group is row entries[first + row0 + t].row of
@@ -1262,6 +1487,24 @@ const UpdateVariant& pick_update(int m, uint32_t max_j) {
     return update_lds(v.MG, max_j) <= kUpdateLdsMax ? v : kUpdate[1];
 }
 
+// Degraded-update variants: the update kernel's row groups over the present
+// parity rows.
+struct DegVariant {
+    int MG;
+    const char* name;
+    void (*fn)(DegArgs);
+};
+#define RS_UPDATE_DEG(MG) {MG, "update_degraded_MG" #MG "_B256", rs_update_degraded_kernel<MG, kBlock, true>}
+const DegVariant kUpdateDeg[] = {RS_UPDATE_DEG(4), RS_UPDATE_DEG(8), RS_UPDATE_DEG(16)};
+#undef RS_UPDATE_DEG
+
+// Per source: its table sub-steps and three addresses.
+size_t update_degraded_lds(int mg, uint32_t max_src) {
+    return static_cast<size_t>(max_src) * (mg / kRowsPerStep) * kStepWords * 4 + 3 * static_cast<size_t>(max_src) * sizeof(void*);
+}
+
+const DegVariant& pick_update_degraded(int m) { return kUpdateDeg[m <= 4 ? 0 : m <= 8 ? 1 : 2]; }
+
 // Combine variants: the update kernel's row groups, chosen from the call's
 // largest nout, so that a job of up to 16 outputs reads its sources once.
 struct CombineVariant {
@@ -1389,6 +1632,47 @@ hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream) {
     const size_t lds = update_lds(static_cast<int>(a.mg), max_j);
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
+
+const char* update_degraded_variant_name(int m) { return pick_update_degraded(m).name; }
+
+bool update_degraded_fused(int m, uint32_t max_src) {
+    return m <= 16 && update_degraded_lds(pick_update_degraded(m).MG, max_src) <= kUpdateLdsMax;
+}
+
+bool plan_update_degraded_launch(DegArgs* a, uint32_t max_src, bool fused) {
+    const DegVariant* v = &pick_update_degraded(static_cast<int>(a->m));
+    // Pair form only: a job too wide for the LDS with row groups of 16 takes
+    // row groups of 8, as the update kernel's.
+    if (!fused && update_degraded_lds(v->MG, max_src) > kUpdateLdsMax) v = &kUpdateDeg[1];
+    const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
+    static const uint32_t iters_cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    a->iters = std::min<uint32_t>(iters_cap, std::max<uint32_t>(total_it, 1));
+    a->chunks = (total_it + a->iters - 1) / a->iters;
+    a->mg = static_cast<uint32_t>(v->MG);
+    a->groups = fused ? 1u : std::max<uint32_t>(1u, (a->m + a->mg - 1) / a->mg);
+    a->commit = fused ? 1u : 0u;
+    const uint64_t blocks = static_cast<uint64_t>(a->njobs) * a->chunks * a->groups;
+    if (blocks > 0x7FFFFFFFull) return false;
+    if (a->xcd == ~0u) a->xcd = a->chunks * a->groups;  // a stripe per XCD region
+    return true;
+}
+
+hipError_t launch_update_degraded(const DegArgs& a, uint32_t max_src, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || max_src == 0) return hipSuccess;
+    const DegVariant* v = nullptr;
+    for (const DegVariant& u : kUpdateDeg)
+        if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
+    const size_t lds = update_degraded_lds(static_cast<int>(a.mg), max_src);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (a.commit && a.groups != 1) return hipErrorInvalidConfiguration;  // in place: one block per column
     hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
     return hipGetLastError();
 }

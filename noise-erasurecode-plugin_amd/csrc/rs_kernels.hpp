@@ -7,6 +7,7 @@
 
 #include "combine_plan.hpp"
 #include "read_plan.hpp"
+#include "update_degraded_plan.hpp"
 #include "update_plan.hpp"
 
 namespace rsmi {
@@ -151,6 +152,51 @@ struct UpdArgs {
 bool plan_update(UpdArgs* a, uint32_t max_j);
 hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream);  // a: planned
 const char* update_variant_name(int m);  // "update_MG4_B256" etc.
+
+// In-place parity update of stripes with missing shards (rs_update_degraded):
+// job b of `jobs` (update_degraded_plan.hpp) patches the present parity rows
+// rows[row_first .. row_first + nrows) of its stripe,
+//     parity[r] ^= sum_c enc[(k + r) * k + shard_c] * (old_c ^ new_c),
+// and never dereferences the slot of an erased shard.  Two forms, per job:
+//   pair form   (pat == kDegNoPattern): the sources are (old, new) pairs as in
+//               the update kernel; old is the entry's slot, or entries[].old
+//               where the caller regenerated it.
+//   decode form (pat = the stripe's pattern in the ctx's pattern cache): the
+//               sources are the pattern's k survivors and the j new buffers,
+//               the old contents of the erased changed shards folded into the
+//               survivors' coefficients (rs_update_degraded_kernel).  Needs
+//               groups == 1: a parity survivor is a source and an output.
+// A block is {job, 4 KiB column chunk, row group of MG present parity rows}.
+struct DegArgs {
+    uint8_t* data;
+    uint8_t* parity;
+    uint64_t data_ss, parity_ss, pitch;  // strided layout, as MatArgs
+    uint32_t ncols16;                    // 16-byte columns per shard
+    uint32_t k, m;
+    const uint8_t* enc;     // [k + m][k] encode matrix, then the exp[512] and log[256] tables (device)
+    const uint8_t* coef;    // [npat][m][k] (the pattern cache, as MatArgs); decode form only
+    const uint32_t* src;    // [npat][k]
+    const DegJob* jobs;     // [njobs] (device), at most one per stripe
+    const DegEntry* entries;  // (device)
+    const uint32_t* rows;     // (device)
+    uint32_t njobs;
+    uint32_t xcd;           // XCD-aware block order, as MatArgs
+    // Filled in by plan_update_degraded_launch:
+    uint32_t chunks, groups, iters;
+    uint32_t mg;      // row-group size of the variant chosen
+    uint32_t commit;  // 1 (one row group): the block stores the new contents of present changed
+                      // shards over the old itself; 0: the caller copies them in behind the kernel
+};
+// Whether one row group and the LDS serve a call of this m whose widest job
+// has max_src sources (UpdateDegradedPlan::max_src) -- the decode form's needs.
+bool update_degraded_fused(int m, uint32_t max_src);
+// Chooses the variant for a->m and fills in the launch plan.  fused: one row
+// group, in-kernel commit, max_src as above; else row groups as the update
+// kernel's, no commit, every job in pair form and max_src = the largest j.
+// false when the grid would exceed 2^31 - 1 blocks.
+bool plan_update_degraded_launch(DegArgs* a, uint32_t max_src, bool fused);
+hipError_t launch_update_degraded(const DegArgs& a, uint32_t max_src, hipStream_t stream);  // a: planned
+const char* update_degraded_variant_name(int m);  // "update_degraded_MG4_B256" etc.
 
 // Caller-chosen combinations (rs_combine): job b of `jobs` (combine_plan.hpp)
 // multiplies its nsrc source buffers by its nout x nsrc coefficients and

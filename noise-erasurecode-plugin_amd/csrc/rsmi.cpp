@@ -39,6 +39,7 @@
 #include "pinned.hpp"
 #include "rs_kernels.hpp"
 #include "scrub.hpp"
+#include "update_degraded_plan.hpp"
 #include "update_plan.hpp"
 
 namespace {
@@ -369,6 +370,7 @@ struct rs_ctx {
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
+    std::atomic<int64_t> update_degraded{0}, update_absorbed{0};         // rs_update_degraded (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1293,6 +1295,9 @@ rsmi::ReadArgs read_args(const rs_ctx* c, const void* data, size_t dss, const vo
     return a;
 }
 
+// Whose counters a read launch feeds.
+enum class ReadFor { kRead, kScrub, kUpdate };
+
 // Launches a planned rs_read_stripes on stream s.  With jobs, pat_mu is held
 // (shared or exclusive) and L.pid holds the built pattern of every job.  The
 // job and entry tables, the jobs' pattern ids and the {src, dst} address pairs
@@ -1301,7 +1306,7 @@ rsmi::ReadArgs read_args(const rs_ctx* c, const void* data, size_t dss, const vo
 // same stream.
 int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
                         size_t pitch, size_t len, const rsmi::ReadPlan& plan, rsmi::ReadArgs a, hipStream_t s,
-                        bool scrub = false) {
+                        ReadFor who = ReadFor::kRead) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size(), ncopy = plan.copies.size();
     size_t max_pid = 0;
     for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
@@ -1346,9 +1351,9 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const
         e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
                                      static_cast<uint32_t>(ncopy), round_up(len, 16), s);
     L.end(s);  // under pat_mu: an eviction waits for these launches
-    if (e == hipSuccess && scrub) {
+    if (e == hipSuccess && who == ReadFor::kScrub) {
         c->scrub_regenerated += static_cast<int64_t>(count);
-    } else if (e == hipSuccess) {
+    } else if (e == hipSuccess && who == ReadFor::kRead) {
         c->read_regenerated += static_cast<int64_t>(count);
         c->read_copied += static_cast<int64_t>(ncopy);
     }
@@ -1360,14 +1365,15 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const
 // come from the cache rs_reconstruct_stripes fills, by reconstruct()'s
 // protocol -- lookups and the launch under a shared lock; only a call that
 // meets new patterns takes it exclusively (to create, build and, past the
-// cap, evict).  A plan without jobs (copies only) takes no lock.  scrub: the
-// call regenerates located shards for rs_correct_degraded, which counts them
-// in a counter of its own.
+// cap, evict).  A plan without jobs (copies only) takes no lock.  who: the
+// call regenerates located shards for rs_correct_degraded (kScrub), which
+// counts them in a counter of its own, or old contents for rs_update_degraded
+// (kUpdate), which counts none.
 int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
                  size_t len, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a, hipStream_t s,
-                 bool scrub = false) {
+                 ReadFor who = ReadFor::kRead) {
     const size_t njobs = plan.jobs.size();
-    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
+    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
     const uint8_t* erased = plan.erased.data();
     size_t missing = 0;
     uint64_t gen = 0;
@@ -1375,7 +1381,7 @@ int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* 
         std::shared_lock<std::shared_mutex> rl(c->pat_mu);
         const int rc = lookup_patterns(c, erased, njobs, L.pid, false, &missing, false, &L.miss_keys);
         if (rc != RS_OK) return rc;
-        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
+        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
         gen = c->evictions;
     }
     std::unique_lock<std::shared_mutex> wl(c->pat_mu);
@@ -1388,7 +1394,7 @@ int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* 
     if (rc != RS_OK) return rc;
     const int st = flush_patterns(c, s, true);
     if (st != RS_OK) return st;
-    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, scrub);
+    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
 }
 
 // ------------------------------------------------------- degraded scrub ----
@@ -1477,6 +1483,158 @@ int check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void*
     const int st = flush_patterns(c, s, true);
     if (st != RS_OK) return st;
     return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
+}
+
+// ------------------------------------------------------ degraded update ----
+// Launches a planned rs_update_degraded on stream s.  fused: the jobs with
+// erased changed shards run in decode form -- pat_mu is held (shared or
+// exclusive) and L.pid holds the built pattern of each of them, in job order
+// -- and the kernel commits the data.  Otherwise every job runs in pair form,
+// the old contents of the x-th erased entry of the entry table at scratch +
+// x * round_up(len, 16), and the new contents of present shards are copied in
+// behind the kernel.  The job, entry and row tables and the copy's {src, dst}
+// address pairs go through the lease's pinned staging into its device buffer
+// in one upload, as update_stripes' tables do.
+int launch_degraded_update(rs_ctx* c, Lease& L, void* data, size_t dss, size_t pitch, size_t len,
+                           const rsmi::UpdateDegradedPlan& plan, rsmi::DegArgs a, bool fused, const uint8_t* scratch,
+                           hipStream_t s) {
+    const size_t njobs = plan.jobs.size(), count = plan.entries.size(), nrows = plan.rows.size();
+    const size_t span = round_up(len, 16);
+    const bool decode = fused && plan.decode_jobs > 0;
+    size_t max_pid = 0;
+    for (size_t b = 0; decode && b < plan.decode_jobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
+    size_t ncopy = 0;
+    if (!a.commit)
+        for (const rsmi::DegEntry& e : plan.entries) ncopy += e.rank == rsmi::kDegPresent;
+    const size_t ent_off = njobs * sizeof(rsmi::DegJob);
+    const size_t row_off = ent_off + count * sizeof(rsmi::DegEntry);
+    const size_t pieces_off = round_up(row_off + nrows * sizeof(uint32_t), 16);
+    const size_t bytes = pieces_off + ncopy * 2 * sizeof(uint64_t);
+    L.begin(s);  // the table buffer's previous readers
+    const bool waited = decode && wait_patterns_for(c, L, max_pid, s);
+    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+    rsmi::DegJob* hj = reinterpret_cast<rsmi::DegJob*>(hb);
+    rsmi::DegEntry* he = reinterpret_cast<rsmi::DegEntry*>(hb + ent_off);
+    std::memcpy(hj, plan.jobs.data(), ent_off);
+    std::memcpy(he, plan.entries.data(), count * sizeof(rsmi::DegEntry));
+    std::memcpy(hb + row_off, plan.rows.data(), nrows * sizeof(uint32_t));
+    uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
+    size_t d = 0, x = 0, q = 0;
+    for (size_t b = 0; b < njobs; ++b) {
+        if (decode && hj[b].jx > 0) hj[b].pat = L.pid[d++];
+        for (uint32_t i = hj[b].first; i < hj[b].first + hj[b].j; ++i) {
+            if (he[i].rank != rsmi::kDegPresent) {
+                if (!fused) he[i].old = reinterpret_cast<uintptr_t>(scratch) + x++ * span;
+            } else if (!a.commit) {
+                pieces[2 * q] = he[i].src;
+                pieces[2 * q + 1] = reinterpret_cast<uintptr_t>(data) + hj[b].stripe * dss + he[i].shard * pitch;
+                ++q;
+            }
+        }
+    }
+    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
+    L.st_stripe.release_after(s);
+    if (e != hipSuccess) {
+        L.end(s);
+        return RS_EDEVICE;
+    }
+    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    a.jobs = reinterpret_cast<const rsmi::DegJob*>(db);
+    a.entries = reinterpret_cast<const rsmi::DegEntry*>(db + ent_off);
+    a.rows = reinterpret_cast<const uint32_t*>(db + row_off);
+    if (decode) {
+        a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
+        a.src = static_cast<const uint32_t*>(c->d_psrc.p);
+    }
+    e = rsmi::launch_update_degraded(a, fused ? plan.max_src : plan.max_j, s);
+    // The pieces hold absolute addresses: offsets from a null base.
+    if (e == hipSuccess && ncopy > 0)
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
+                                     static_cast<uint32_t>(ncopy), span, s);
+    L.end(s);  // under pat_mu: an eviction waits for these launches
+    if (e == hipSuccess) {
+        c->update_degraded += static_cast<int64_t>(njobs);
+        c->update_absorbed += static_cast<int64_t>(plan.absorbed);
+    }
+    if (waited && e == hipSuccess) seen_patterns(c, L);
+    return hip_status(e);
+}
+
+// rs_update_degraded on stream s with lease L (m > 0, some listed stripe
+// degraded).  The fused path: one launch; the patterns of the jobs with erased
+// changed shards come from the cache rs_reconstruct_stripes fills, by
+// read_stripes()'s protocol, and a plan without such jobs takes no lock.  The
+// slow path (update_degraded_fused() says no: m > 16, or the widest job's
+// tables pass the LDS): the old contents of the erased changed shards are
+// regenerated into the lease's scratch by the read launch, then every job runs
+// in pair form with a copy commit.
+int update_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                    const rsmi::UpdateDegradedPlan& plan, hipStream_t s) {
+    rsmi::DegArgs a{};
+    a.data = static_cast<uint8_t*>(data);
+    a.parity = static_cast<uint8_t*>(parity);
+    a.data_ss = dss;
+    a.parity_ss = pss;
+    a.pitch = pitch;
+    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
+    a.k = static_cast<uint32_t>(c->k);
+    a.m = static_cast<uint32_t>(c->m);
+    a.enc = dev_enc(c);
+    a.njobs = static_cast<uint32_t>(plan.jobs.size());
+    a.xcd = c->xcd_update;
+    const bool fused = rsmi::update_degraded_fused(c->m, plan.max_src);
+    if (!rsmi::plan_update_degraded_launch(&a, fused ? plan.max_src : plan.max_j, fused)) return RS_EINVAL;
+    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
+    if (!a.commit && plan.entries.size() * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull)
+        return RS_EINVAL;
+    if (!fused) {
+        const uint8_t* scratch = nullptr;
+        if (plan.decode_jobs > 0) {
+            const size_t span = round_up(len, 16);
+            rsmi::ReadPlan rp;
+            rp.erased = plan.erased;
+            for (const rsmi::DegJob& job : plan.jobs) {
+                if (job.jx == 0) continue;
+                rp.jobs.push_back(rsmi::ReadJob{job.stripe, static_cast<uint32_t>(rp.entries.size()), job.jx});
+                for (uint32_t i = job.first + job.j - job.jx; i < job.first + job.j; ++i)
+                    rp.entries.push_back(rsmi::ReadEntry{0u, plan.entries[i].rank, 0u});
+                rp.max_j = std::max(rp.max_j, job.jx);
+            }
+            rsmi::ReadArgs ra = read_args(c, data, dss, parity, pss, pitch, len, rp.jobs.size());
+            if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
+            L.begin(s);  // the scratch's previous readers
+            if (!L.d_scrub.reserve_on(rp.entries.size() * span, s)) return RS_ENOMEM;
+            scratch = static_cast<const uint8_t*>(L.d_scrub.p);
+            for (size_t x = 0; x < rp.entries.size(); ++x) rp.entries[x].dst = reinterpret_cast<uintptr_t>(scratch) + x * span;
+            const int rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, ReadFor::kUpdate);
+            if (rc != RS_OK) return rc;
+        }
+        return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, false, scratch, s);
+    }
+    const size_t nd = plan.decode_jobs;
+    if (nd == 0) return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
+    const uint8_t* flags = plan.erased.data();
+    size_t missing = 0;
+    uint64_t gen = 0;
+    {
+        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
+        const int rc = lookup_patterns(c, flags, nd, L.pid, false, &missing, false, &L.miss_keys);
+        if (rc != RS_OK) return rc;
+        if (missing == 0) return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
+        gen = c->evictions;
+    }
+    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
+    bool stale = c->evictions != gen;
+    if (c->pat_index.size() + missing > c->pat_cap) {
+        evict_patterns(c);
+        stale = true;
+    }
+    const int rc = lookup_patterns(c, flags, nd, L.pid, true, nullptr, !stale);
+    if (rc != RS_OK) return rc;
+    const int st = flush_patterns(c, s, true);
+    if (st != RS_OK) return st;
+    return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
 }
 
 // rs_correct_degraded on stream s with lease L: correct_stripes' loop with
@@ -1590,7 +1748,7 @@ int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, 
         if (rc != RS_OK) return rc;
         rsmi::ReadArgs ra = read_args(c, data, dss, parity, pss, pitch, len, rp.jobs.size());
         if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
-        rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, true);
+        rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, ReadFor::kScrub);
         if (rc != RS_OK) return rc;
         if (rewritten)
             for (uint32_t i : live)
@@ -2900,6 +3058,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 4) return rsmi::read_variant_name(c->k);
     if (which == 5) return rsmi::check_variant_name(c->k);
     if (which == 6) return rsmi::combine_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
+    if (which == 7) return rsmi::update_degraded_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2958,6 +3117,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_SCRUB_REGENERATED: return c->scrub_regenerated.load();
         case RS_STAT_COMBINE_JOBS: return c->combine_jobs.load();
         case RS_STAT_COMBINE_ROWS: return c->combine_rows.load();
+        case RS_STAT_UPDATE_DEGRADED: return c->update_degraded.load();
+        case RS_STAT_UPDATE_ABSORBED: return c->update_absorbed.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3221,6 +3382,41 @@ int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t ps
     LeaseGuard lg(c);
     if (!lg.L) return RS_ENOMEM;
     return update_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
+}
+
+int rs_update_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                       size_t stripes, const uint8_t* erased, const rs_shard_update* updates, size_t count,
+                       void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!updates || !erased) return RS_EINVAL;
+    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    if (c->set) {
+        rs_ctx* mc = routed(c, data);
+        return mc ? rs_update_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, updates, count, stream)
+                  : RS_EINVAL;
+    }
+    // No src may lie in the call's data or parity region (rs_update_stripes):
+    // a defect of the list, so the planner looks for it before it counts any
+    // stripe's erasures.
+    const size_t span = round_up(len, 16);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
+    const rsmi::UpdateExtent ext{
+        d0, d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span, p0,
+        c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0, span};
+    rsmi::UpdateDegradedPlan plan;
+    const int rc = rsmi::plan_update_degraded(c->k, c->n, stripes, erased, updates, count, &ext, &plan);
+    if (rc != RS_OK) return rc;
+    // No flag set in any listed stripe: the call is rs_update_stripes.  So is
+    // one without parity: every changed shard is present (an erased one was
+    // refused) and only the data is overwritten.
+    if (!plan.degraded || c->m == 0)
+        return rs_update_stripes(c, data, dss, parity, pss, pitch, len, stripes, updates, count, stream);
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    LeaseGuard lg(c);
+    if (!lg.L) return RS_ENOMEM;
+    return update_degraded(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
 }
 
 int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch, size_t len,

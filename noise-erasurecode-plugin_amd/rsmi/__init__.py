@@ -39,7 +39,7 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
-    "rs_verify_degraded", "rs_correct_degraded", "rs_combine", "rs_pattern_survivors",
+    "rs_verify_degraded", "rs_correct_degraded", "rs_update_degraded", "rs_combine", "rs_pattern_survivors",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -159,6 +159,7 @@ def _lib() -> ctypes.CDLL:
             "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
             "rs_update_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
+            "rs_update_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardUpdate), sz, vp]),
             "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_verify_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
@@ -529,6 +530,24 @@ class FEC:
                                         pitch, shard_len, stripes, arr, len(updates), stream or None),
                "rs_update_stripes")
 
+    def update_degraded(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                        pitch: int, shard_len: int, stripes: int, erased: bytes, updates: Sequence[tuple],
+                        stream: int = 0) -> None:
+        """rs_update_degraded: update_stripes for stripes with missing shards
+        (erased: stripes * n flags).  Present parity shards are patched in
+        place; a present changed shard takes its new contents; an erased one
+        is left alone -- its old contents are regenerated from the stripe's
+        survivors for the patch and its new ones live in the parity until
+        reconstruct_stripes with the same flags produces them.  Erased slots
+        are never dereferenced.  Enqueued on stream."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        arr = updates if isinstance(updates, ctypes.Array) else shard_updates(updates)
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_update_degraded(self._h, data_ptr, data_stride, parity_ptr or None, parity_stride,
+                                         pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), arr,
+                                         len(updates), stream or None), "rs_update_degraded")
+
     def read_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
                      pitch: int, shard_len: int, stripes: int, erased: bytes, reads: Sequence[tuple],
                      stream: int = 0) -> None:
@@ -586,7 +605,8 @@ class FEC:
      STAT_ENCODES_IN_PLACE, STAT_DECODES_IN_PLACE, STAT_REC_STRIPES_TABLE, STAT_REC_STRIPES_SYNDROME,
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
-     STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS) = range(20)
+     STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
+     STAT_UPDATE_ABSORBED) = range(22)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
