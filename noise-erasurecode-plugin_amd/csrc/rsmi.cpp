@@ -472,30 +472,74 @@ const uint2* first_stripe_desc(const rs_ctx* c, const void* dev) {
     return reinterpret_cast<const uint2*>(static_cast<const uint8_t*>(dev) + PatLayout(c, 1).sw);
 }
 
-bool check_stripes_args(const rs_ctx* c, const void* data, size_t dss, const void* parity,
-                        size_t pss, size_t pitch, size_t len) {
-    auto al = [](uintptr_t v) { return (v & 15u) == 0; };
-    if (!data || (!parity && c->m > 0)) return false;
-    if (!al(reinterpret_cast<uintptr_t>(data)) || !al(reinterpret_cast<uintptr_t>(parity)))
-        return false;
-    if (!al(dss) || !al(pss) || !al(pitch)) return false;
-    if (pitch < round_up(len, 16)) return false;
-    if (round_up(len, 16) / 16 >= (size_t(1) << 28)) return false;  // 32-bit column offsets
+// The strided stripe layout of a call: shard i of stripe s at data + s * dss +
+// i * pitch for i < k, at parity + s * pss + (i - k) * pitch otherwise, `len`
+// bytes each.  Pointer mode (a table of shard addresses instead) has no
+// regions: ptrs().
+struct StripeView {
+    void* data;
+    size_t dss;
+    void* parity;
+    size_t pss;
+    size_t pitch, len;
+    static StripeView of(const void* data, size_t dss, const void* parity, size_t pss, size_t pitch, size_t len) {
+        return {const_cast<void*>(data), dss, const_cast<void*>(parity), pss, pitch, len};
+    }
+    static StripeView ptrs(size_t pitch, size_t len) { return {nullptr, 0, nullptr, 0, pitch, len}; }
+    size_t span() const { return round_up(len, 16); }  // the bytes of a shard the kernels move
+    uint32_t ncols16() const { return static_cast<uint32_t>(span() / 16); }
+    // Address of shard id of a stripe.
+    uintptr_t slot(uint64_t stripe, size_t id, int k) const {
+        return id < static_cast<size_t>(k) ? reinterpret_cast<uintptr_t>(data) + stripe * dss + id * pitch
+                                           : reinterpret_cast<uintptr_t>(parity) + stripe * pss + (id - k) * pitch;
+    }
+    // The data region [d0, d1) and the parity region [p0, p1) of `stripes` stripes.
+    rsmi::UpdateExtent extent(size_t stripes, int k, int m) const {
+        const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
+        return {d0, d0 + (stripes - 1) * dss + static_cast<size_t>(k - 1) * pitch + span(), p0,
+                m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(m - 1) * pitch + span() : p0, span()};
+    }
+};
+
+// Does [a, a + span) touch the call's data or parity region?
+bool touches(const rsmi::UpdateExtent& x, uintptr_t a) {
+    const uintptr_t a1 = a + x.span;
+    return (a < x.d1 && x.d0 < a1) || (a < x.p1 && x.p0 < a1);
+}
+
+// launch_copy_pieces runs a block per (piece, 4 KiB chunk): do they fit its grid?
+bool copy_pieces_fit(size_t pieces, uint32_t ncols16) {
+    return pieces * ((static_cast<uint64_t>(ncols16) + 255) / 256) <= 0x7FFFFFFFull;
+}
+
+bool check_stripes_args(const rs_ctx* c, const StripeView& v) {
+    auto al = [](uintptr_t x) { return (x & 15u) == 0; };
+    if (!v.data || (!v.parity && c->m > 0)) return false;
+    if (!al(reinterpret_cast<uintptr_t>(v.data)) || !al(reinterpret_cast<uintptr_t>(v.parity))) return false;
+    if (!al(v.dss) || !al(v.pss) || !al(v.pitch)) return false;
+    if (v.pitch < v.span()) return false;
+    if (v.span() / 16 >= (size_t(1) << 28)) return false;  // 32-bit column offsets
     return true;
 }
 
-rsmi::MatArgs base_args(const rs_ctx* c, void* data, size_t dss, void* parity, size_t pss,
-                        size_t pitch, size_t len, size_t stripes) {
-    rsmi::MatArgs a{};
-    a.data = static_cast<uint8_t*>(data);
-    a.parity = static_cast<uint8_t*>(parity);
-    a.data_ss = dss;
-    a.parity_ss = pss;
-    a.pitch = pitch;
-    a.stripes = stripes;
-    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
+// The layout fields MatArgs, ReadArgs, UpdArgs and DegArgs share.
+template <class Args>
+Args layout_args(const rs_ctx* c, const StripeView& v) {
+    Args a{};
+    a.data = static_cast<uint8_t*>(v.data);
+    a.parity = static_cast<uint8_t*>(v.parity);
+    a.data_ss = v.dss;
+    a.parity_ss = v.pss;
+    a.pitch = v.pitch;
+    a.ncols16 = v.ncols16();
     a.k = static_cast<uint32_t>(c->k);
     a.m = static_cast<uint32_t>(c->m);
+    return a;
+}
+
+rsmi::MatArgs base_args(const rs_ctx* c, const StripeView& v, size_t stripes) {
+    rsmi::MatArgs a = layout_args<rsmi::MatArgs>(c, v);
+    a.stripes = stripes;
     a.xcd = c->xcd_split_rec;  // split-table reconstruct: a stripe per XCD region by default
     return a;
 }
@@ -541,8 +585,6 @@ hipError_t launch_encode(const rs_ctx* c, const rsmi::MatArgs& a, hipStream_t s)
 // code's encode is bit-sliced and a reconstruct twin was generated (k <= 64).
 // RSMI_BITSLICE_REC=0 keeps the split-table kernel (A/B runs).
 // Read at rs_new, like RSMI_BITSLICE.
-bool use_bitslice_rec(const rs_ctx* c) { return c->bitslice_rec; }
-
 bool pick_bitslice_rec(const rsmi::BitsliceKernel* b) {
     const char* e = std::getenv("RSMI_BITSLICE_REC");
     if (e && std::atoi(e) == 0) return false;
@@ -614,7 +656,17 @@ int create_pattern(rs_ctx* c, const PatKey& key, int e) {
 
 constexpr uint32_t kMissing = 0xFFFFFFFFu;
 
-void rollback_patterns(rs_ctx* c);
+// Undoes the patterns created since the last successful build (pat_mu
+// exclusive): after a failed lookup or build they must not stay in the index,
+// or a later call would find them and launch on rows never written.
+void rollback_patterns(rs_ctx* c) {
+    if (c->h_cnt.size() == c->uploaded) return;
+    c->pat_index.drop_from(static_cast<int>(c->uploaded));
+    c->h_cnt.resize(c->uploaded);
+    c->h_lo.resize(c->uploaded);
+    c->h_mask.resize(c->uploaded);
+    c->h_key.clear();
+}
 
 // Pattern id of every stripe into pid.  With `create` (pat_mu exclusive)
 // missing patterns are added (and rolled back if the call fails); without
@@ -686,18 +738,6 @@ void evict_patterns(rs_ctx* c) {
     ++c->tables_gen;
 }
 
-// Undoes the patterns created since the last successful build (pat_mu
-// exclusive): after a failed lookup or build they must not stay in the index,
-// or a later call would find them and launch on rows never written.
-void rollback_patterns(rs_ctx* c) {
-    if (c->h_cnt.size() == c->uploaded) return;
-    c->pat_index.drop_from(static_cast<int>(c->uploaded));
-    c->h_cnt.resize(c->uploaded);
-    c->h_lo.resize(c->uploaded);
-    c->h_mask.resize(c->uploaded);
-    c->h_key.clear();
-}
-
 const uint8_t* dev_enc(const rs_ctx* c) { return static_cast<const uint8_t*>(c->d_gf.p); }
 // 2 KiB of zeros: the address the bit-sliced reconstruct loads for absent
 // inputs (one wave's window, so those loads hit in L2 instead of HBM).
@@ -710,7 +750,8 @@ void wait_patterns(rs_ctx* c, hipStream_t s) {
     if (c->pat_ev_valid) (void)hipStreamWaitEvent(s, c->pat_ev, 0);
 }
 
-// launch_reconstruct's wait (pat_mu held; L.begin(s) already queued): only
+// The wait of a launch that reads pattern rows (launch_reconstruct,
+// upload_tables; pat_mu held; L.begin(s) already queued): only
 // when a pattern the launch reads -- ids up to max_pid -- was built after
 // the lease's last wait, or the tables moved since.  Otherwise the rows are
 // complete before the lease's previous launch, which s follows through
@@ -721,7 +762,8 @@ void wait_patterns(rs_ctx* c, hipStream_t s) {
 // (seen_patterns) only after L.end(s), so a failed launch leaves no claim.
 // Skipping the wait is sound only while three invariants hold (ADVICE r04;
 // tests/test_gpu_concurrency.py test_watermark_reuse_while_tables_move):
-//   1. launch_reconstruct holds pat_mu from this wait until L.end(s), so no
+//   1. the launch holds pat_mu (with_patterns) from this wait until L.end(s)
+//      (finish_launch), so no
 //      build, growth or eviction can slip between the check and the launch;
 //   2. a lease's dev_pending is never cleared, so L.begin(s) always orders s
 //      after the lease's previous launch (which followed the rows it read);
@@ -830,11 +872,88 @@ void set_cache_patterns(const rs_ctx* c, rsmi::MatArgs& a) {
     a.dst_stride = static_cast<uint32_t>(dst_stride(c));
 }
 
+// The pattern-cache protocol, for every call that launches on cached decode
+// patterns: the patterns of `count` erasure-flag rows [count][n] into L.pid,
+// then launch().  Lookups and the launches that read the device tables run
+// under a shared lock; only a call that meets new patterns takes pat_mu
+// exclusively (to create, build and, past the cap, evict), and then launches
+// under it.  count == 0: launch() reads no pattern and runs without a lock.
+template <class Launch>
+int with_patterns(rs_ctx* c, Lease& L, const uint8_t* flags, size_t count, hipStream_t s, Launch launch) {
+    if (count == 0) return launch();
+    size_t missing = 0;
+    uint64_t gen = 0;
+    {
+        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
+        const int rc = lookup_patterns(c, flags, count, L.pid, false, &missing, false, &L.miss_keys);
+        if (rc != RS_OK) return rc;
+        if (missing == 0) return launch();
+        gen = c->evictions;
+    }
+    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
+    // Only the rows the shared pass missed are looked up again, unless the
+    // cache was evicted meanwhile (ids found then are stale).  `missing`
+    // counts distinct new patterns (an upper bound: another caller may have
+    // created some of them since).
+    bool stale = c->evictions != gen;
+    if (c->pat_index.size() + missing > c->pat_cap) {
+        evict_patterns(c);
+        stale = true;
+    }
+    const int rc = lookup_patterns(c, flags, count, L.pid, true, nullptr, !stale);
+    if (rc != RS_OK) return rc;
+    const int st = flush_patterns(c, s, true);
+    if (st != RS_OK) return st;
+    return launch();
+}
+
+// A call's tables on the device: the lease's buffer and whether the upload
+// waited for the pattern builds (finish_launch).
+struct Tables {
+    const uint8_t* dev = nullptr;
+    bool waited = false;
+};
+
+// Stages a call's tables on stream s: orders s after the lease's previous
+// device use, waits for the builds of the patterns L.pid[0 .. npids) if the
+// lease has not seen them (wait_patterns_for; pat_mu held when npids > 0),
+// then fill(block) writes `bytes` bytes of the lease's pinned block and one
+// copy takes them to its device buffer.  bytes == 0: nothing to upload.  A
+// failed copy ends the lease.
+template <class Fill>
+int upload_tables(rs_ctx* c, Lease& L, size_t npids, size_t bytes, hipStream_t s, Tables* t, Fill fill) {
+    size_t max_pid = 0;
+    for (size_t b = 0; b < npids; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
+    L.begin(s);  // the table buffer's previous readers
+    t->waited = npids > 0 && wait_patterns_for(c, L, max_pid, s);
+    if (bytes > 0) {
+        if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
+        fill(static_cast<uint8_t*>(L.st_stripe.p));
+        const hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, L.st_stripe.p, bytes, hipMemcpyHostToDevice, s);
+        L.st_stripe.release_after(s);
+        if (e != hipSuccess) {
+            L.end(s);
+            return RS_EDEVICE;
+        }
+    }
+    t->dev = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    return RS_OK;
+}
+
+// After a call's last launch on s (under pat_mu when it read pattern rows:
+// an eviction waits for these launches): the lease's event, and its
+// watermark if the call waited for the builds and succeeded.
+int finish_launch(const rs_ctx* c, Lease& L, hipStream_t s, bool waited, int rc) {
+    L.end(s);
+    if (waited && rc == RS_OK) seen_patterns(c, L);
+    return rc;
+}
+
 // Launches the reconstruct of `stripes` whose patterns are in L.pid (pat_mu
 // held, shared or exclusive, and every pattern built): stripe descriptors
 // through L's staging and device buffer, then one launch per kernel.
-int launch_reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch,
-                       size_t len, size_t stripes, const uint64_t* shard_ptrs, hipStream_t s) {
+int launch_reconstruct(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint64_t* shard_ptrs,
+                       hipStream_t s) {
     const std::vector<uint32_t>& pid = L.pid;
     int max_e = 0;
     for (size_t i = 0; i < stripes; ++i) max_e = std::max<int>(max_e, static_cast<int>(c->h_cnt[pid[i]]));
@@ -852,11 +971,11 @@ int launch_reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity
     // one RS(64,16) 64 KiB stripe reconstructs in 0.0375 ms instead of 0.048
     // (profiles/r05c/, r05d/lat_*.json); past ~16 stripes its VALU cost loses.
     size_t erased_stripes = 0;
-    if (use_bitslice_rec(c) && c->small_split > 0)
+    if (c->bitslice_rec && c->small_split > 0)
         for (size_t i = 0; i < stripes && erased_stripes <= c->small_split; ++i) erased_stripes += c->h_cnt[pid[i]] != 0;
-    const bool small_split = use_bitslice_rec(c) && c->small_split > 0 && erased_stripes <= c->small_split;
-    const int split_e = use_bitslice_rec(c) && !small_split ? c->bitslice_rec_min_e : (c->m + 1);
-    const int T = use_bitslice_rec(c) && !small_split ? c->n_tops : 0;
+    const bool small_split = c->bitslice_rec && c->small_split > 0 && erased_stripes <= c->small_split;
+    const int split_e = c->bitslice_rec && !small_split ? c->bitslice_rec_min_e : (c->m + 1);
+    const int T = c->bitslice_rec && !small_split ? c->n_tops : 0;
     const size_t nk = static_cast<size_t>(T) + 2;
     auto kernel_of = [&](uint32_t p) -> size_t {
         if (static_cast<int>(c->h_cnt[p]) < split_e) return 0;
@@ -940,11 +1059,14 @@ int launch_reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity
         if (!L.d_stripe_pat.reserve_on(desc_bytes, s)) return RS_ENOMEM;
         e = hipMemcpyAsync(L.d_stripe_pat.p, desc, desc_bytes, hipMemcpyHostToDevice, s);
         L.st_stripe.release_after(s);
-        if (e != hipSuccess) return RS_EDEVICE;
+        if (e != hipSuccess) {
+            L.end(s);
+            return RS_EDEVICE;
+        }
     }
     const uint2* d_desc = inl ? nullptr : static_cast<const uint2*>(L.d_stripe_pat.p);
     if (count[0] > 0) {
-        rsmi::MatArgs a = base_args(c, data, dss, parity, pss, pitch, len, count[0]);
+        rsmi::MatArgs a = base_args(c, v, count[0]);
         set_cache_patterns(c, a);
         a.stripe_desc = d_desc;
         if (inl) {
@@ -959,7 +1081,7 @@ int launch_reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity
         if (!count[kk]) continue;
         // Generated bit-sliced reconstruct (syndromes through the fixed
         // encode network, bitslice.hpp): same descriptors and pattern cache.
-        rsmi::MatArgs a = base_args(c, data, dss, parity, pss, pitch, len, count[kk]);
+        rsmi::MatArgs a = base_args(c, v, count[kk]);
         set_cache_patterns(c, a);
         rsmi::BitsliceRecArgs b{};
         b.data = a.data;
@@ -989,45 +1111,34 @@ int launch_reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity
         b.xcd = c->xcd;
         e = kk <= static_cast<size_t>(T) ? c->bitslice->rec_top_launch[kk - 1](b, s) : c->bitslice->reconstruct(b, s);
     }
-    L.end(s);  // under pat_mu: an eviction waits for these launches
     if (e == hipSuccess) {
         c->rec_stripes_table += static_cast<int64_t>(count[0]);
         c->rec_stripes_syndrome += static_cast<int64_t>(used - count[0]);
     }
-    if (waited && e == hipSuccess) seen_patterns(c, L);
-    return hip_status(e);
+    return finish_launch(c, L, s, waited, hip_status(e));
 }
 
-// Batched reconstruct on stream s with lease L: lookups and launches under
-// a shared lock; only a call that meets new patterns takes it exclusively
-// (to create, build and, past the cap, evict).
-int reconstruct(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch,
-                size_t len, size_t stripes, const uint8_t* erased, const uint64_t* shard_ptrs, hipStream_t s) {
-    size_t missing = 0;
-    uint64_t gen = 0;
-    {
-        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
-        const int rc = lookup_patterns(c, erased, stripes, L.pid, false, &missing, false, &L.miss_keys);
-        if (rc != RS_OK) return rc;
-        if (missing == 0) return launch_reconstruct(c, L, data, dss, parity, pss, pitch, len, stripes, shard_ptrs, s);
-        gen = c->evictions;
-    }
-    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
-    // Only the stripes the shared pass missed are looked up again, unless
-    // the cache was evicted meanwhile (ids found then are stale).  `missing`
-    // counts distinct new patterns (an upper bound: another caller may have
-    // created some of them since).
-    bool stale = c->evictions != gen;
-    if (c->pat_index.size() + missing > c->pat_cap) {
-        evict_patterns(c);
-        stale = true;
-    }
-    const int rc = lookup_patterns(c, erased, stripes, L.pid, true, nullptr, !stale);
-    if (rc != RS_OK) return rc;
-    const int st = flush_patterns(c, s, true);
-    if (st != RS_OK) return st;
-    return launch_reconstruct(c, L, data, dss, parity, pss, pitch, len, stripes, shard_ptrs, s);
+// Batched reconstruct on stream s with lease L, the patterns of the stripes'
+// erasure flags from the cache (with_patterns).  shard_ptrs: pointer mode, the
+// device table of shard addresses [stripes][n].
+int reconstruct(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint8_t* erased,
+                const uint64_t* shard_ptrs, hipStream_t s) {
+    return with_patterns(c, L, erased, stripes, s,
+                         [&] { return launch_reconstruct(c, L, v, stripes, shard_ptrs, s); });
 }
+
+// A call's device and lease: the context's device is current and a lease
+// held until scope exit, or error() says why not.
+struct CallScope {
+    DeviceGuard g;
+    rs_ctx* c;
+    Lease* L;
+    explicit CallScope(rs_ctx* ctx) : g(ctx->device), c(ctx), L(g.ok ? acquire_lease(ctx) : nullptr) {}
+    ~CallScope() {
+        if (L) release_lease(c, L);
+    }
+    int error() const { return !g.ok ? RS_EDEVICE : !L ? RS_ENOMEM : RS_OK; }
+};
 
 // Pointer-mode reconstruct from a HOST table of shard addresses
 // [stripes][n] (rs_reconstruct_spread: one member's stripes): the table goes
@@ -1038,11 +1149,9 @@ int reconstruct_host_table(rs_ctx* c, const uint64_t* tab, size_t len, size_t st
     const size_t bytes = stripes * static_cast<size_t>(c->n) * sizeof(uint64_t);
     for (size_t i = 0; i < stripes * static_cast<size_t>(c->n); ++i)
         if (tab[i] & 15u) return RS_EINVAL;  // the kernels move 16-byte vectors
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    Lease& L = *lg.L;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    Lease& L = *sc.L;
     L.begin(s);  // the lease's table buffer may last have been read on another stream
     if (!L.st_pieces.acquire(bytes) || !L.d_pieces.reserve_on(bytes, s)) return RS_ENOMEM;
     std::memcpy(L.st_pieces.p, tab, bytes);
@@ -1052,244 +1161,105 @@ int reconstruct_host_table(rs_ctx* c, const uint64_t* tab, size_t len, size_t st
         L.end(s);
         return RS_EDEVICE;
     }
-    const int rc = reconstruct(c, L, nullptr, 0, nullptr, 0, round_up(len, 16), len, stripes, erased,
+    const int rc = reconstruct(c, L, StripeView::ptrs(round_up(len, 16), len), stripes, erased,
                                static_cast<const uint64_t*>(L.d_pieces.p), s);
     L.end(s);  // also when nothing was launched: the table copy wrote d_pieces on s
     return rc;
 }
 
-// ---------------------------------------------------------------- scrub ----
+// --------------------------------------------------------------- verify ----
 // Verify launch on stream s: first_bad[0 .. stripes) is preset to
 // RS_VERIFY_CLEAN, then the verify twin of the split-table encode kernel
 // checks every stripe (desc == nullptr) or the `count` stripes listed in desc
 // (device, {stripe index, 0 << 8 | m}).
-int launch_verify_stripes(const rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
-                          size_t len, size_t stripes, const uint2* desc, size_t count, uint32_t* first_bad,
-                          hipStream_t s) {
+int launch_verify_stripes(const rs_ctx* c, const StripeView& v, size_t stripes, const uint2* desc, size_t count,
+                          uint32_t* first_bad, hipStream_t s) {
     if (hipMemsetAsync(first_bad, 0xFF, stripes * sizeof(uint32_t), s) != hipSuccess) return RS_EDEVICE;
     if (c->m == 0 || count == 0) return RS_OK;
-    rsmi::MatArgs a = base_args(c, const_cast<void*>(data), dss, const_cast<void*>(parity), pss, pitch, len, count);
+    rsmi::MatArgs a = base_args(c, v, count);
     set_patterns(c, 1, c->d_encpat.p, a);
     a.stripe_desc = desc;
     a.xcd = c->xcd_split_enc;
-    return hip_status(rsmi::launch_verify(a, first_bad, static_cast<uint32_t>(len), s));
-}
-
-// rs_correct_stripes on stream s with lease L.  Device workspace (L.d_scrub)
-// and its pinned mirror (L.st_scrub), all O(stripes):
-//   first_bad u32 [stripes] | list uint2 [stripes] | columns u8 [stripes * n]
-// `list` holds the gather's {stripe, byte offset} pairs, then the re-verify's
-// {stripe, m} descriptors of the same live stripes.
-int correct_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
-                    size_t stripes, int* status, uint8_t* rewritten, hipStream_t s) {
-    const size_t n = static_cast<size_t>(c->n);
-    const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
-    const size_t cols_off = list_off + stripes * sizeof(uint2);
-    const size_t bytes = cols_off + stripes * n;
-    L.begin(s);
-    if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
-    uint8_t* const hb = static_cast<uint8_t*>(L.st_scrub.p);
-    uint8_t* const db = static_cast<uint8_t*>(L.d_scrub.p);
-    uint32_t* const h_fb = reinterpret_cast<uint32_t*>(hb);
-    uint2* const h_list = reinterpret_cast<uint2*>(hb + list_off);
-    uint8_t* const h_cols = hb + cols_off;
-    uint32_t* const d_fb = reinterpret_cast<uint32_t*>(db);
-    uint2* const d_list = reinterpret_cast<uint2*>(db + list_off);
-    uint8_t* const d_cols = db + cols_off;
-    // Every exit records the lease's last device use.
-    struct End {
-        Lease& L;
-        hipStream_t s;
-        ~End() { L.end(s); }
-    } end_guard{L, s};
-
-    // Verdicts of the stripes verified last (all, or the live list) to the host.
-    auto fetch_verdicts = [&]() -> int {
-        if (hipMemcpyAsync(h_fb, d_fb, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return RS_EDEVICE;
-        return RS_OK;
-    };
-    int rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, d_fb, s);
-    if (rc == RS_OK) rc = fetch_verdicts();
-    if (rc != RS_OK) return rc;
-    std::vector<uint32_t> live;
-    for (size_t i = 0; i < stripes; ++i)
-        if (h_fb[i] != RS_VERIFY_CLEAN) live.push_back(static_cast<uint32_t>(i));
-    if (live.empty()) return RS_OK;
-
-    // known: every shard located so far (the set L of the stripe; reported
-    // through `rewritten`); erased: the same for the live stripes only, what
-    // each round's reconstruct regenerates.
-    std::vector<uint8_t> known(stripes * n, 0), erased(stripes * n, 0);
-    bool failed = false;
-    auto give_up = [&](uint32_t i) {
-        if (status) status[i] = RS_ETOO_MANY_ERRORS;
-        std::fill_n(erased.begin() + static_cast<size_t>(i) * n, n, uint8_t(0));
-        failed = true;
-    };
-    const rsmi::MatArgs ga = base_args(c, data, dss, parity, pss, pitch, len, stripes);
-    for (int round = 0; round < c->m && !live.empty(); ++round) {
-        // The column at each live stripe's first inconsistent offset.
-        for (size_t j = 0; j < live.size(); ++j) {
-            if (h_fb[live[j]] >= len) return RS_EDEVICE;  // never: verify reports offsets below shard_len
-            h_list[j] = make_uint2(live[j], h_fb[live[j]]);
-        }
-        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess ||
-            rsmi::launch_gather_columns(ga, d_list, static_cast<uint32_t>(live.size()), d_cols, s) != hipSuccess ||
-            hipMemcpyAsync(h_cols, d_cols, live.size() * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return RS_EDEVICE;
-        size_t kept = 0;
-        for (size_t j = 0; j < live.size(); ++j) {
-            const uint32_t i = live[j];
-            uint8_t* kn = &known[static_cast<size_t>(i) * n];
-            // An inconsistent column always holds a wrong share outside the
-            // set, so a round that locates none is a failure too.
-            if (rsmi::scrub_locate(c->k, c->n, kn, h_cols + j * n) <= 0) {
-                give_up(i);
-                continue;
-            }
-            std::copy(kn, kn + n, erased.begin() + static_cast<size_t>(i) * n);
-            live[kept++] = i;
-        }
-        live.resize(kept);
-        if (live.empty()) break;
-        // All of every live stripe's set, in one batched reconstruct.
-        rc = reconstruct(c, L, data, dss, parity, pss, pitch, len, stripes, erased.data(), nullptr, s);
-        if (rc != RS_OK) return rc;
-        if (rewritten)
-            for (uint32_t i : live) std::copy_n(&known[static_cast<size_t>(i) * n], n, rewritten + static_cast<size_t>(i) * n);
-        // Verify the live stripes again, through the stripe list.
-        for (size_t j = 0; j < live.size(); ++j) h_list[j] = make_uint2(live[j], static_cast<uint32_t>(c->m));
-        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
-            return RS_EDEVICE;
-        rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, d_list, live.size(), d_fb, s);
-        if (rc == RS_OK) rc = fetch_verdicts();
-        if (rc != RS_OK) return rc;
-        kept = 0;
-        for (uint32_t i : live) {
-            if (h_fb[i] == RS_VERIFY_CLEAN) std::fill_n(erased.begin() + static_cast<size_t>(i) * n, n, uint8_t(0));
-            else live[kept++] = i;
-        }
-        live.resize(kept);
-    }
-    for (uint32_t i : live) give_up(i);  // still inconsistent after m rounds
-    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+    return hip_status(rsmi::launch_verify(a, first_bad, static_cast<uint32_t>(v.len), s));
 }
 
 // --------------------------------------------------------------- update ----
 // rs_update_stripes on stream s with lease L: the planned job and entry
-// tables (and, for the copy commit, the {src, dst} address pairs) go through
-// the lease's pinned staging into its device buffer in one upload, as
-// launch_reconstruct's descriptors do; then the update kernel, then -- when
+// tables (and, for the copy commit, the {src, dst} address pairs) go to the
+// device in one upload (upload_tables); then the update kernel, then -- when
 // the kernel could not commit the data itself -- the copy of the new shards
 // into place, on the same stream behind it.
-int update_stripes(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
-                   const rsmi::UpdatePlan& plan, hipStream_t s) {
+int update_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdatePlan& plan, hipStream_t s) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size();
-    rsmi::UpdArgs a{};
-    a.data = static_cast<uint8_t*>(data);
-    a.parity = static_cast<uint8_t*>(parity);
-    a.data_ss = dss;
-    a.parity_ss = pss;
-    a.pitch = pitch;
-    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
-    a.k = static_cast<uint32_t>(c->k);
-    a.m = static_cast<uint32_t>(c->m);
-    a.enc = static_cast<const uint8_t*>(c->d_gf.p);
+    rsmi::UpdArgs a = layout_args<rsmi::UpdArgs>(c, v);
+    a.enc = dev_enc(c);
     a.njobs = static_cast<uint32_t>(njobs);
     a.xcd = c->xcd_update;
     if (!rsmi::plan_update(&a, plan.max_j)) return RS_EINVAL;
     const bool copy_commit = c->m == 0 || !a.commit;
-    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
-    if (copy_commit && count * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull) return RS_EINVAL;
+    if (copy_commit && !copy_pieces_fit(count, a.ncols16)) return RS_EINVAL;
     const size_t ent_off = njobs * sizeof(rsmi::UpdateJob);
     const size_t pieces_off = ent_off + count * sizeof(rsmi::UpdateEntry);
     const size_t bytes = pieces_off + (copy_commit ? count * 2 * sizeof(uint64_t) : 0);
-    L.begin(s);  // the table buffer's previous readers
-    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
-    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
-    std::memcpy(hb, plan.jobs.data(), ent_off);
-    std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::UpdateEntry));
-    if (copy_commit) {
+    Tables t;
+    const int up = upload_tables(c, L, 0, bytes, s, &t, [&](uint8_t* hb) {
+        std::memcpy(hb, plan.jobs.data(), ent_off);
+        std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::UpdateEntry));
+        if (!copy_commit) return;
         uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
         for (const rsmi::UpdateJob& job : plan.jobs)
             for (uint32_t i = job.first; i < job.first + job.j; ++i) {
                 pieces[2 * i] = plan.entries[i].src;
-                pieces[2 * i + 1] = reinterpret_cast<uintptr_t>(data) + job.stripe * dss + plan.entries[i].shard * pitch;
+                pieces[2 * i + 1] = v.slot(job.stripe, plan.entries[i].shard, c->k);
             }
-    }
-    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
-    L.st_stripe.release_after(s);
-    if (e != hipSuccess) {
-        L.end(s);
-        return RS_EDEVICE;
-    }
-    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
-    a.jobs = reinterpret_cast<const rsmi::UpdateJob*>(db);
-    a.entries = reinterpret_cast<const rsmi::UpdateEntry*>(db + ent_off);
+    });
+    if (up != RS_OK) return up;
+    a.jobs = reinterpret_cast<const rsmi::UpdateJob*>(t.dev);
+    a.entries = reinterpret_cast<const rsmi::UpdateEntry*>(t.dev + ent_off);
+    hipError_t e = hipSuccess;
     if (c->m > 0) e = rsmi::launch_update(a, plan.max_j, s);
     // The pieces hold absolute addresses: offsets from a null base.
     if (e == hipSuccess && copy_commit)
-        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
-                                     static_cast<uint32_t>(count), round_up(len, 16), s);
-    L.end(s);
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                     static_cast<uint32_t>(count), v.span(), s);
     if (e == hipSuccess) {
         c->update_stripes += static_cast<int64_t>(njobs);
         if (copy_commit) ++c->update_copy_commits;
     }
-    return hip_status(e);
+    return finish_launch(c, L, s, false, hip_status(e));
 }
 
 // -------------------------------------------------------------- combine ----
 // rs_combine on stream s with lease L: the planned job, address and
-// coefficient tables go through the lease's pinned staging into its device
-// buffer in one upload, as update_stripes' tables do; then the combine kernel.
+// coefficient tables in one upload (upload_tables); then the combine kernel.
 int combine(rs_ctx* c, Lease& L, const rsmi::CombinePlan& plan, rsmi::CombArgs a, hipStream_t s) {
     const size_t njobs = plan.jobs.size();
     const size_t addr_off = njobs * sizeof(rsmi::CombineJob);
     const size_t coef_off = addr_off + plan.addrs.size() * sizeof(uint64_t);
     const size_t bytes = coef_off + plan.coef.size();
-    L.begin(s);  // the table buffer's previous readers
-    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
-    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
-    std::memcpy(hb, plan.jobs.data(), addr_off);
-    std::memcpy(hb + addr_off, plan.addrs.data(), coef_off - addr_off);
-    std::memcpy(hb + coef_off, plan.coef.data(), plan.coef.size());
-    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
-    L.st_stripe.release_after(s);
-    if (e != hipSuccess) {
-        L.end(s);
-        return RS_EDEVICE;
-    }
-    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
-    a.jobs = reinterpret_cast<const rsmi::CombineJob*>(db);
-    a.addrs = reinterpret_cast<const uint64_t*>(db + addr_off);
-    a.coef = db + coef_off;
-    e = rsmi::launch_combine(a, plan.max_nsrc, s);
-    L.end(s);
+    Tables t;
+    const int up = upload_tables(c, L, 0, bytes, s, &t, [&](uint8_t* hb) {
+        std::memcpy(hb, plan.jobs.data(), addr_off);
+        std::memcpy(hb + addr_off, plan.addrs.data(), coef_off - addr_off);
+        std::memcpy(hb + coef_off, plan.coef.data(), plan.coef.size());
+    });
+    if (up != RS_OK) return up;
+    a.jobs = reinterpret_cast<const rsmi::CombineJob*>(t.dev);
+    a.addrs = reinterpret_cast<const uint64_t*>(t.dev + addr_off);
+    a.coef = t.dev + coef_off;
+    const hipError_t e = rsmi::launch_combine(a, plan.max_nsrc, s);
     if (e == hipSuccess) {
         c->combine_jobs += static_cast<int64_t>(njobs);
         c->combine_rows += static_cast<int64_t>(plan.rows);
     }
-    return hip_status(e);
+    return finish_launch(c, L, s, false, hip_status(e));
 }
 
 // --------------------------------------------------------- degraded read ----
 // The read kernel's arguments for `njobs` jobs over the strided layout (the
 // launch plan and the device tables are filled in later).
-rsmi::ReadArgs read_args(const rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
-                         size_t len, size_t njobs) {
-    rsmi::ReadArgs a{};
-    a.data = static_cast<const uint8_t*>(data);
-    a.parity = static_cast<const uint8_t*>(parity);
-    a.data_ss = dss;
-    a.parity_ss = pss;
-    a.pitch = pitch;
-    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
-    a.k = static_cast<uint32_t>(c->k);
-    a.m = static_cast<uint32_t>(c->m);
+rsmi::ReadArgs read_args(const rs_ctx* c, const StripeView& v, size_t njobs) {
+    rsmi::ReadArgs a = layout_args<rsmi::ReadArgs>(c, v);
     a.njobs = static_cast<uint32_t>(njobs);
     a.xcd = c->xcd_split_rec;
     return a;
@@ -1301,188 +1271,115 @@ enum class ReadFor { kRead, kScrub, kUpdate };
 // Launches a planned rs_read_stripes on stream s.  With jobs, pat_mu is held
 // (shared or exclusive) and L.pid holds the built pattern of every job.  The
 // job and entry tables, the jobs' pattern ids and the {src, dst} address pairs
-// of the wanted present shards go through the lease's pinned staging into its
-// device buffer in one upload; then the read kernel, then the copies, on the
-// same stream.
-int launch_read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
-                        size_t pitch, size_t len, const rsmi::ReadPlan& plan, rsmi::ReadArgs a, hipStream_t s,
-                        ReadFor who = ReadFor::kRead) {
+// of the wanted present shards go to the device in one upload (upload_tables);
+// then the read kernel, then the copies, on the same stream.
+int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan& plan, rsmi::ReadArgs a,
+                        hipStream_t s, ReadFor who) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size(), ncopy = plan.copies.size();
-    size_t max_pid = 0;
-    for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
     const size_t ent_off = njobs * sizeof(rsmi::ReadJob);
     const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
     const size_t pieces_off = round_up(pat_off + njobs * sizeof(uint32_t), 16);
     const size_t bytes = pieces_off + ncopy * 2 * sizeof(uint64_t);
-    L.begin(s);  // the table buffer's previous readers
-    const bool waited = njobs > 0 && wait_patterns_for(c, L, max_pid, s);
-    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
-    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
-    if (njobs > 0) {
-        std::memcpy(hb, plan.jobs.data(), ent_off);
-        std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
-        std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
-    }
-    uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
-    for (size_t i = 0; i < ncopy; ++i) {
-        const rsmi::ReadCopy& r = plan.copies[i];
-        pieces[2 * i] = r.shard < static_cast<uint32_t>(c->k)
-                            ? reinterpret_cast<uintptr_t>(data) + r.stripe * dss + r.shard * pitch
-                            : reinterpret_cast<uintptr_t>(parity) + r.stripe * pss + (r.shard - c->k) * pitch;
-        pieces[2 * i + 1] = r.dst;
-    }
-    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
-    L.st_stripe.release_after(s);
-    if (e != hipSuccess) {
-        L.end(s);
-        return RS_EDEVICE;
-    }
-    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
+    Tables t;
+    const int up = upload_tables(c, L, njobs, bytes, s, &t, [&](uint8_t* hb) {
+        if (njobs > 0) {
+            std::memcpy(hb, plan.jobs.data(), ent_off);
+            std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
+            std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+        }
+        uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
+        for (size_t i = 0; i < ncopy; ++i) {
+            pieces[2 * i] = v.slot(plan.copies[i].stripe, plan.copies[i].shard, c->k);
+            pieces[2 * i + 1] = plan.copies[i].dst;
+        }
+    });
+    if (up != RS_OK) return up;
+    hipError_t e = hipSuccess;
     if (njobs > 0) {
         a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
         a.src = static_cast<const uint32_t*>(c->d_psrc.p);
-        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(db);
-        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(db + ent_off);
-        a.pats = reinterpret_cast<const uint32_t*>(db + pat_off);
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
         e = rsmi::launch_read(a, s);
     }
     // The pieces hold absolute addresses: offsets from a null base.
     if (e == hipSuccess && ncopy > 0)
-        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
-                                     static_cast<uint32_t>(ncopy), round_up(len, 16), s);
-    L.end(s);  // under pat_mu: an eviction waits for these launches
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                     static_cast<uint32_t>(ncopy), v.span(), s);
     if (e == hipSuccess && who == ReadFor::kScrub) {
         c->scrub_regenerated += static_cast<int64_t>(count);
     } else if (e == hipSuccess && who == ReadFor::kRead) {
         c->read_regenerated += static_cast<int64_t>(count);
         c->read_copied += static_cast<int64_t>(ncopy);
     }
-    if (waited && e == hipSuccess) seen_patterns(c, L);
-    return hip_status(e);
+    return finish_launch(c, L, s, t.waited, hip_status(e));
 }
 
 // rs_read_stripes on stream s with lease L: the patterns of the jobs' stripes
-// come from the cache rs_reconstruct_stripes fills, by reconstruct()'s
-// protocol -- lookups and the launch under a shared lock; only a call that
-// meets new patterns takes it exclusively (to create, build and, past the
-// cap, evict).  A plan without jobs (copies only) takes no lock.  who: the
-// call regenerates located shards for rs_correct_degraded (kScrub), which
-// counts them in a counter of its own, or old contents for rs_update_degraded
-// (kUpdate), which counts none.
-int read_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
-                 size_t len, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a, hipStream_t s,
-                 ReadFor who = ReadFor::kRead) {
-    const size_t njobs = plan.jobs.size();
-    if (njobs == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
-    const uint8_t* erased = plan.erased.data();
-    size_t missing = 0;
-    uint64_t gen = 0;
-    {
-        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
-        const int rc = lookup_patterns(c, erased, njobs, L.pid, false, &missing, false, &L.miss_keys);
-        if (rc != RS_OK) return rc;
-        if (missing == 0) return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
-        gen = c->evictions;
-    }
-    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
-    bool stale = c->evictions != gen;
-    if (c->pat_index.size() + missing > c->pat_cap) {
-        evict_patterns(c);
-        stale = true;
-    }
-    const int rc = lookup_patterns(c, erased, njobs, L.pid, true, nullptr, !stale);
-    if (rc != RS_OK) return rc;
-    const int st = flush_patterns(c, s, true);
-    if (st != RS_OK) return st;
-    return launch_read_stripes(c, L, data, dss, parity, pss, pitch, len, plan, a, s, who);
+// come from the cache rs_reconstruct_stripes fills (with_patterns; a plan
+// without jobs -- copies only -- takes no lock).  who: the call regenerates
+// located shards for rs_correct_degraded (kScrub), which counts them in a
+// counter of its own, or old contents for rs_update_degraded (kUpdate), which
+// counts none.
+int read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a,
+                 hipStream_t s, ReadFor who = ReadFor::kRead) {
+    return with_patterns(c, L, plan.erased.data(), plan.jobs.size(), s,
+                         [&] { return launch_read_stripes(c, L, v, plan, a, s, who); });
 }
 
-// ------------------------------------------------------- degraded scrub ----
+// ------------------------------------------------------- degraded verify ----
 // Launches a planned degraded verify on stream s.  With jobs, pat_mu is held
 // (shared or exclusive) and L.pid holds the built pattern of every job.  The
 // intact stripes' list, the job and entry tables and the jobs' pattern ids go
-// through the lease's pinned staging into its device buffer in one upload;
-// then first_bad's preset and the verify kernel over the intact stripes
-// (launch_verify_stripes), then the check kernel over the degraded ones.
-int launch_check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss,
-                         size_t pitch, size_t len, size_t stripes, const rsmi::CheckPlan& plan, rsmi::ReadArgs a,
-                         uint32_t* first_bad, hipStream_t s) {
+// to the device in one upload (upload_tables; a plan of saturated stripes only
+// has nothing to upload); then first_bad's preset and the verify kernel over
+// the intact stripes (launch_verify_stripes), then the check kernel over the
+// degraded ones.
+int launch_check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const rsmi::CheckPlan& plan,
+                         rsmi::ReadArgs a, uint32_t* first_bad, hipStream_t s) {
     const size_t nintact = plan.intact.size(), njobs = plan.jobs.size(), count = plan.entries.size();
-    size_t max_pid = 0;
-    for (size_t b = 0; b < njobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
     const size_t job_off = round_up(nintact * sizeof(uint2), 16);
     const size_t ent_off = job_off + njobs * sizeof(rsmi::ReadJob);
     const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
     const size_t bytes = pat_off + njobs * sizeof(uint32_t);
-    L.begin(s);  // the table buffer's previous readers
-    const bool waited = njobs > 0 && wait_patterns_for(c, L, max_pid, s);
-    hipError_t e = hipSuccess;
-    if (bytes > 0) {
-        if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
-        uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
+    Tables t;
+    const int up = upload_tables(c, L, njobs, bytes, s, &t, [&](uint8_t* hb) {
         uint2* desc = reinterpret_cast<uint2*>(hb);
         for (size_t i = 0; i < nintact; ++i) desc[i] = make_uint2(plan.intact[i], static_cast<uint32_t>(c->m));
-        if (njobs > 0) {
-            std::memcpy(hb + job_off, plan.jobs.data(), njobs * sizeof(rsmi::ReadJob));
-            std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
-            std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
-        }
-        e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
-        L.st_stripe.release_after(s);
-        if (e != hipSuccess) {
-            L.end(s);
-            return RS_EDEVICE;
-        }
-    }
-    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
-    int rc = launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, reinterpret_cast<const uint2*>(db),
-                                   nintact, first_bad, s);
+        if (njobs == 0) return;
+        std::memcpy(hb + job_off, plan.jobs.data(), njobs * sizeof(rsmi::ReadJob));
+        std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
+        std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+    });
+    if (up != RS_OK) return up;
+    int rc = launch_verify_stripes(c, v, stripes, reinterpret_cast<const uint2*>(t.dev), nintact, first_bad, s);
     if (rc == RS_OK && njobs > 0) {
         a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
         a.src = static_cast<const uint32_t*>(c->d_psrc.p);
-        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(db + job_off);
-        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(db + ent_off);
-        a.pats = reinterpret_cast<const uint32_t*>(db + pat_off);
-        rc = hip_status(rsmi::launch_check(a, first_bad, static_cast<uint32_t>(len), s));
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev + job_off);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
+        rc = hip_status(rsmi::launch_check(a, first_bad, static_cast<uint32_t>(v.len), s));
     }
-    L.end(s);  // under pat_mu: an eviction waits for these launches
     if (rc == RS_OK) c->check_stripes += static_cast<int64_t>(njobs);
-    if (waited && rc == RS_OK) seen_patterns(c, L);
-    return rc;
+    return finish_launch(c, L, s, t.waited, rc);
 }
 
 // A planned degraded verify on stream s with lease L: the patterns of the
 // jobs' compact flags (the erasure sets X') come from the cache
-// rs_reconstruct_stripes fills, by read_stripes()'s protocol.  A plan without
-// jobs takes no lock.
-int check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
-                  size_t len, size_t stripes, const rsmi::CheckPlan& plan, uint32_t* first_bad, hipStream_t s) {
-    const size_t njobs = plan.jobs.size();
-    rsmi::ReadArgs a = read_args(c, data, dss, parity, pss, pitch, len, njobs);
+// rs_reconstruct_stripes fills (with_patterns; a plan without jobs takes no
+// lock).
+int check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const rsmi::CheckPlan& plan,
+                  uint32_t* first_bad, hipStream_t s) {
+    rsmi::ReadArgs a = read_args(c, v, plan.jobs.size());
     if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
-    if (njobs == 0) return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
-    const uint8_t* flags = plan.flags.data();
-    size_t missing = 0;
-    uint64_t gen = 0;
-    {
-        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
-        const int rc = lookup_patterns(c, flags, njobs, L.pid, false, &missing, false, &L.miss_keys);
-        if (rc != RS_OK) return rc;
-        if (missing == 0)
-            return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
-        gen = c->evictions;
-    }
-    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
-    bool stale = c->evictions != gen;
-    if (c->pat_index.size() + missing > c->pat_cap) {
-        evict_patterns(c);
-        stale = true;
-    }
-    const int rc = lookup_patterns(c, flags, njobs, L.pid, true, nullptr, !stale);
-    if (rc != RS_OK) return rc;
-    const int st = flush_patterns(c, s, true);
-    if (st != RS_OK) return st;
-    return launch_check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, plan, a, first_bad, s);
+    return with_patterns(c, L, plan.flags.data(), plan.jobs.size(), s,
+                         [&] { return launch_check_stripes(c, L, v, stripes, plan, a, first_bad, s); });
+}
+
+rsmi::CheckLayout check_layout(const StripeView& v) {
+    return {reinterpret_cast<uintptr_t>(v.data), reinterpret_cast<uintptr_t>(v.parity), v.dss, v.pss, v.pitch};
 }
 
 // ------------------------------------------------------ degraded update ----
@@ -1491,18 +1388,14 @@ int check_stripes(rs_ctx* c, Lease& L, const void* data, size_t dss, const void*
 // exclusive) and L.pid holds the built pattern of each of them, in job order
 // -- and the kernel commits the data.  Otherwise every job runs in pair form,
 // the old contents of the x-th erased entry of the entry table at scratch +
-// x * round_up(len, 16), and the new contents of present shards are copied in
-// behind the kernel.  The job, entry and row tables and the copy's {src, dst}
-// address pairs go through the lease's pinned staging into its device buffer
-// in one upload, as update_stripes' tables do.
-int launch_degraded_update(rs_ctx* c, Lease& L, void* data, size_t dss, size_t pitch, size_t len,
-                           const rsmi::UpdateDegradedPlan& plan, rsmi::DegArgs a, bool fused, const uint8_t* scratch,
-                           hipStream_t s) {
+// x * span, and the new contents of present shards are copied in behind the
+// kernel.  The job, entry and row tables and the copy's {src, dst} address
+// pairs go to the device in one upload (upload_tables).
+int launch_degraded_update(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdateDegradedPlan& plan,
+                           rsmi::DegArgs a, bool fused, const uint8_t* scratch, hipStream_t s) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size(), nrows = plan.rows.size();
-    const size_t span = round_up(len, 16);
+    const size_t span = v.span();
     const bool decode = fused && plan.decode_jobs > 0;
-    size_t max_pid = 0;
-    for (size_t b = 0; decode && b < plan.decode_jobs; ++b) max_pid = std::max<size_t>(max_pid, L.pid[b]);
     size_t ncopy = 0;
     if (!a.commit)
         for (const rsmi::DegEntry& e : plan.entries) ncopy += e.rank == rsmi::kDegPresent;
@@ -1510,149 +1403,110 @@ int launch_degraded_update(rs_ctx* c, Lease& L, void* data, size_t dss, size_t p
     const size_t row_off = ent_off + count * sizeof(rsmi::DegEntry);
     const size_t pieces_off = round_up(row_off + nrows * sizeof(uint32_t), 16);
     const size_t bytes = pieces_off + ncopy * 2 * sizeof(uint64_t);
-    L.begin(s);  // the table buffer's previous readers
-    const bool waited = decode && wait_patterns_for(c, L, max_pid, s);
-    if (!L.st_stripe.acquire(bytes) || !L.d_stripe_pat.reserve_on(bytes, s)) return RS_ENOMEM;
-    uint8_t* const hb = static_cast<uint8_t*>(L.st_stripe.p);
-    rsmi::DegJob* hj = reinterpret_cast<rsmi::DegJob*>(hb);
-    rsmi::DegEntry* he = reinterpret_cast<rsmi::DegEntry*>(hb + ent_off);
-    std::memcpy(hj, plan.jobs.data(), ent_off);
-    std::memcpy(he, plan.entries.data(), count * sizeof(rsmi::DegEntry));
-    std::memcpy(hb + row_off, plan.rows.data(), nrows * sizeof(uint32_t));
-    uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
-    size_t d = 0, x = 0, q = 0;
-    for (size_t b = 0; b < njobs; ++b) {
-        if (decode && hj[b].jx > 0) hj[b].pat = L.pid[d++];
-        for (uint32_t i = hj[b].first; i < hj[b].first + hj[b].j; ++i) {
-            if (he[i].rank != rsmi::kDegPresent) {
-                if (!fused) he[i].old = reinterpret_cast<uintptr_t>(scratch) + x++ * span;
-            } else if (!a.commit) {
-                pieces[2 * q] = he[i].src;
-                pieces[2 * q + 1] = reinterpret_cast<uintptr_t>(data) + hj[b].stripe * dss + he[i].shard * pitch;
-                ++q;
+    Tables t;
+    const int up = upload_tables(c, L, decode ? plan.decode_jobs : 0, bytes, s, &t, [&](uint8_t* hb) {
+        rsmi::DegJob* hj = reinterpret_cast<rsmi::DegJob*>(hb);
+        rsmi::DegEntry* he = reinterpret_cast<rsmi::DegEntry*>(hb + ent_off);
+        std::memcpy(hj, plan.jobs.data(), ent_off);
+        std::memcpy(he, plan.entries.data(), count * sizeof(rsmi::DegEntry));
+        std::memcpy(hb + row_off, plan.rows.data(), nrows * sizeof(uint32_t));
+        uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
+        size_t d = 0, x = 0, q = 0;
+        for (size_t b = 0; b < njobs; ++b) {
+            if (decode && hj[b].jx > 0) hj[b].pat = L.pid[d++];
+            for (uint32_t i = hj[b].first; i < hj[b].first + hj[b].j; ++i) {
+                if (he[i].rank != rsmi::kDegPresent) {
+                    if (!fused) he[i].old = reinterpret_cast<uintptr_t>(scratch) + x++ * span;
+                } else if (!a.commit) {
+                    pieces[2 * q] = he[i].src;
+                    pieces[2 * q + 1] = v.slot(hj[b].stripe, he[i].shard, c->k);
+                    ++q;
+                }
             }
         }
-    }
-    hipError_t e = hipMemcpyAsync(L.d_stripe_pat.p, hb, bytes, hipMemcpyHostToDevice, s);
-    L.st_stripe.release_after(s);
-    if (e != hipSuccess) {
-        L.end(s);
-        return RS_EDEVICE;
-    }
-    const uint8_t* const db = static_cast<const uint8_t*>(L.d_stripe_pat.p);
-    a.jobs = reinterpret_cast<const rsmi::DegJob*>(db);
-    a.entries = reinterpret_cast<const rsmi::DegEntry*>(db + ent_off);
-    a.rows = reinterpret_cast<const uint32_t*>(db + row_off);
+    });
+    if (up != RS_OK) return up;
+    a.jobs = reinterpret_cast<const rsmi::DegJob*>(t.dev);
+    a.entries = reinterpret_cast<const rsmi::DegEntry*>(t.dev + ent_off);
+    a.rows = reinterpret_cast<const uint32_t*>(t.dev + row_off);
     if (decode) {
         a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
         a.src = static_cast<const uint32_t*>(c->d_psrc.p);
     }
-    e = rsmi::launch_update_degraded(a, fused ? plan.max_src : plan.max_j, s);
+    hipError_t e = rsmi::launch_update_degraded(a, fused ? plan.max_src : plan.max_j, s);
     // The pieces hold absolute addresses: offsets from a null base.
     if (e == hipSuccess && ncopy > 0)
-        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(db + pieces_off),
+        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
                                      static_cast<uint32_t>(ncopy), span, s);
-    L.end(s);  // under pat_mu: an eviction waits for these launches
     if (e == hipSuccess) {
         c->update_degraded += static_cast<int64_t>(njobs);
         c->update_absorbed += static_cast<int64_t>(plan.absorbed);
     }
-    if (waited && e == hipSuccess) seen_patterns(c, L);
-    return hip_status(e);
+    return finish_launch(c, L, s, t.waited, hip_status(e));
 }
 
 // rs_update_degraded on stream s with lease L (m > 0, some listed stripe
 // degraded).  The fused path: one launch; the patterns of the jobs with erased
-// changed shards come from the cache rs_reconstruct_stripes fills, by
-// read_stripes()'s protocol, and a plan without such jobs takes no lock.  The
-// slow path (update_degraded_fused() says no: m > 16, or the widest job's
-// tables pass the LDS): the old contents of the erased changed shards are
-// regenerated into the lease's scratch by the read launch, then every job runs
-// in pair form with a copy commit.
-int update_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
-                    const rsmi::UpdateDegradedPlan& plan, hipStream_t s) {
-    rsmi::DegArgs a{};
-    a.data = static_cast<uint8_t*>(data);
-    a.parity = static_cast<uint8_t*>(parity);
-    a.data_ss = dss;
-    a.parity_ss = pss;
-    a.pitch = pitch;
-    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
-    a.k = static_cast<uint32_t>(c->k);
-    a.m = static_cast<uint32_t>(c->m);
+// changed shards come from the cache rs_reconstruct_stripes fills
+// (with_patterns; a plan without such jobs takes no lock).  The slow path
+// (update_degraded_fused() says no: m > 16, or the widest job's tables pass
+// the LDS): the old contents of the erased changed shards are regenerated into
+// the lease's scratch by the read launch, then every job runs in pair form
+// with a copy commit.
+int update_degraded(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdateDegradedPlan& plan, hipStream_t s) {
+    rsmi::DegArgs a = layout_args<rsmi::DegArgs>(c, v);
     a.enc = dev_enc(c);
     a.njobs = static_cast<uint32_t>(plan.jobs.size());
     a.xcd = c->xcd_update;
     const bool fused = rsmi::update_degraded_fused(c->m, plan.max_src);
     if (!rsmi::plan_update_degraded_launch(&a, fused ? plan.max_src : plan.max_j, fused)) return RS_EINVAL;
-    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
-    if (!a.commit && plan.entries.size() * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull)
-        return RS_EINVAL;
-    if (!fused) {
-        const uint8_t* scratch = nullptr;
-        if (plan.decode_jobs > 0) {
-            const size_t span = round_up(len, 16);
-            rsmi::ReadPlan rp;
-            rp.erased = plan.erased;
-            for (const rsmi::DegJob& job : plan.jobs) {
-                if (job.jx == 0) continue;
-                rp.jobs.push_back(rsmi::ReadJob{job.stripe, static_cast<uint32_t>(rp.entries.size()), job.jx});
-                for (uint32_t i = job.first + job.j - job.jx; i < job.first + job.j; ++i)
-                    rp.entries.push_back(rsmi::ReadEntry{0u, plan.entries[i].rank, 0u});
-                rp.max_j = std::max(rp.max_j, job.jx);
-            }
-            rsmi::ReadArgs ra = read_args(c, data, dss, parity, pss, pitch, len, rp.jobs.size());
-            if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
-            L.begin(s);  // the scratch's previous readers
-            if (!L.d_scrub.reserve_on(rp.entries.size() * span, s)) return RS_ENOMEM;
-            scratch = static_cast<const uint8_t*>(L.d_scrub.p);
-            for (size_t x = 0; x < rp.entries.size(); ++x) rp.entries[x].dst = reinterpret_cast<uintptr_t>(scratch) + x * span;
-            const int rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, ReadFor::kUpdate);
-            if (rc != RS_OK) return rc;
+    if (!a.commit && !copy_pieces_fit(plan.entries.size(), a.ncols16)) return RS_EINVAL;
+    if (fused)
+        return with_patterns(c, L, plan.erased.data(), plan.decode_jobs, s,
+                             [&] { return launch_degraded_update(c, L, v, plan, a, true, nullptr, s); });
+    const uint8_t* scratch = nullptr;
+    if (plan.decode_jobs > 0) {
+        const size_t span = v.span();
+        rsmi::ReadPlan rp;
+        rp.erased = plan.erased;
+        for (const rsmi::DegJob& job : plan.jobs) {
+            if (job.jx == 0) continue;
+            rp.jobs.push_back(rsmi::ReadJob{job.stripe, static_cast<uint32_t>(rp.entries.size()), job.jx});
+            for (uint32_t i = job.first + job.j - job.jx; i < job.first + job.j; ++i)
+                rp.entries.push_back(rsmi::ReadEntry{0u, plan.entries[i].rank, 0u});
+            rp.max_j = std::max(rp.max_j, job.jx);
         }
-        return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, false, scratch, s);
-    }
-    const size_t nd = plan.decode_jobs;
-    if (nd == 0) return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
-    const uint8_t* flags = plan.erased.data();
-    size_t missing = 0;
-    uint64_t gen = 0;
-    {
-        std::shared_lock<std::shared_mutex> rl(c->pat_mu);
-        const int rc = lookup_patterns(c, flags, nd, L.pid, false, &missing, false, &L.miss_keys);
+        rsmi::ReadArgs ra = read_args(c, v, rp.jobs.size());
+        if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
+        L.begin(s);  // the scratch's previous readers
+        if (!L.d_scrub.reserve_on(rp.entries.size() * span, s)) return RS_ENOMEM;
+        scratch = static_cast<const uint8_t*>(L.d_scrub.p);
+        for (size_t x = 0; x < rp.entries.size(); ++x) rp.entries[x].dst = reinterpret_cast<uintptr_t>(scratch) + x * span;
+        const int rc = read_stripes(c, L, v, rp, ra, s, ReadFor::kUpdate);
         if (rc != RS_OK) return rc;
-        if (missing == 0) return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
-        gen = c->evictions;
     }
-    std::unique_lock<std::shared_mutex> wl(c->pat_mu);
-    bool stale = c->evictions != gen;
-    if (c->pat_index.size() + missing > c->pat_cap) {
-        evict_patterns(c);
-        stale = true;
-    }
-    const int rc = lookup_patterns(c, flags, nd, L.pid, true, nullptr, !stale);
-    if (rc != RS_OK) return rc;
-    const int st = flush_patterns(c, s, true);
-    if (st != RS_OK) return st;
-    return launch_degraded_update(c, L, data, dss, pitch, len, plan, a, true, nullptr, s);
+    return launch_degraded_update(c, L, v, plan, a, false, scratch, s);
 }
 
-// rs_correct_degraded on stream s with lease L: correct_stripes' loop with
-// the erasure sets X known from the start.  Device workspace (L.d_scrub) and
-// its pinned mirror (L.st_scrub), all O(stripes):
+// ---------------------------------------------------------------- scrub ----
+// rs_correct_stripes (erased == nullptr) and rs_correct_degraded (the erasure
+// sets X known from the start) on stream s with lease L.  Device workspace
+// (L.d_scrub) and its pinned mirror (L.st_scrub), all O(stripes):
 //   first_bad u32 [stripes] | list uint2 [stripes] | columns u8 [stripes * n] | flags u8 [stripes * n]
-// `list` holds the gather's {stripe, byte offset} pairs and `flags` the X of
-// the same live stripes.  The verifies go through check_stripes over the live
-// list; the located set L of a stripe is regenerated in place by the read
-// path with the flags X + L, wanted L and every dst the shard's own slot, so
-// the slots of X are neither read nor written.
-int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
-                     size_t stripes, const uint8_t* erased, int* status, uint8_t* rewritten, hipStream_t s) {
+// `list` holds the gather's {stripe, byte offset} pairs, then -- without X --
+// the re-verify's {stripe, m} descriptors of the same live stripes; `flags`
+// (only with X) holds the X of the live stripes.  With X the verifies go
+// through check_stripes over the live list, and the located set L of a stripe
+// is regenerated in place by the read path with the flags X + L, wanted L and
+// every dst the shard's own slot, so the slots of X are neither read nor
+// written; without, by one batched reconstruct of every live stripe's L.
+int scrub_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint8_t* erased, int* status,
+                  uint8_t* rewritten, hipStream_t s) {
     const size_t n = static_cast<size_t>(c->n);
     const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
     const size_t cols_off = list_off + stripes * sizeof(uint2);
     const size_t flag_off = cols_off + stripes * n;
-    const size_t bytes = flag_off + stripes * n;
+    const size_t bytes = flag_off + (erased ? stripes * n : 0);
     L.begin(s);
     if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
     uint8_t* const hb = static_cast<uint8_t*>(L.st_scrub.p);
@@ -1672,14 +1526,20 @@ int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, 
         ~End() { L.end(s); }
     } end_guard{L, s};
 
-    const rsmi::CheckLayout lay{reinterpret_cast<uintptr_t>(data), reinterpret_cast<uintptr_t>(parity), dss, pss,
-                                pitch};
     rsmi::CheckPlan cp;
-    // Degraded verify of all stripes (list == nullptr) or the listed ones, and
-    // the verdicts to the host.
+    // Verify of all stripes (list == nullptr) or the listed ones, and the
+    // verdicts to the host.
     auto verify = [&](const uint32_t* list, size_t count) -> int {
-        int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, lay, &cp);
-        if (rc == RS_OK) rc = check_stripes(c, L, data, dss, parity, pss, pitch, len, stripes, cp, d_fb, s);
+        int rc;
+        if (erased) {
+            rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), &cp);
+            if (rc == RS_OK) rc = check_stripes(c, L, v, stripes, cp, d_fb, s);
+        } else {
+            for (size_t j = 0; j < count; ++j) h_list[j] = make_uint2(list[j], static_cast<uint32_t>(c->m));
+            if (list && hipMemcpyAsync(d_list, h_list, count * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
+                return RS_EDEVICE;
+            rc = launch_verify_stripes(c, v, stripes, list ? d_list : nullptr, list ? count : stripes, d_fb, s);
+        }
         if (rc != RS_OK) return rc;
         if (hipMemcpyAsync(h_fb, d_fb, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
@@ -1695,34 +1555,41 @@ int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, 
 
     // known: X plus every shard located so far (the set L of the stripe;
     // `rewritten` reports known minus X).
-    std::vector<uint8_t> known(stripes * n);
-    for (size_t i = 0; i < stripes * n; ++i) known[i] = erased[i] != 0 ? 1 : 0;
+    std::vector<uint8_t> known(stripes * n, 0);
+    if (erased)
+        for (size_t i = 0; i < stripes * n; ++i) known[i] = erased[i] != 0 ? 1 : 0;
     bool failed = false;
     auto give_up = [&](uint32_t i) {
         if (status) status[i] = RS_ETOO_MANY_ERRORS;
         failed = true;
     };
-    const rsmi::MatArgs ga = base_args(c, data, dss, parity, pss, pitch, len, stripes);
-    const size_t span = round_up(len, 16);
+    const rsmi::MatArgs ga = base_args(c, v, stripes);
+    // What a round regenerates: without X, `regen` -- the known of the live
+    // stripes, nothing for the others; with X, `reads` -- the located shards.
+    std::vector<uint8_t> regen;
     std::vector<rs_shard_read> reads;
     rsmi::ReadPlan rp;
     for (int round = 0; round < c->m && !live.empty(); ++round) {
-        // The column at each live stripe's first inconsistent offset, without
-        // the missing shards.
+        // The column at each live stripe's first inconsistent offset (without
+        // the missing shards).
         for (size_t j = 0; j < live.size(); ++j) {
-            if (h_fb[live[j]] >= len) return RS_EDEVICE;  // never: the check reports offsets below shard_len
+            if (h_fb[live[j]] >= v.len) return RS_EDEVICE;  // never: the verdicts are offsets below shard_len
             h_list[j] = make_uint2(live[j], h_fb[live[j]]);
-            for (size_t id = 0; id < n; ++id) h_flags[j * n + id] = erased[live[j] * n + id] != 0 ? 1 : 0;
+            if (erased)
+                for (size_t id = 0; id < n; ++id) h_flags[j * n + id] = erased[live[j] * n + id] != 0 ? 1 : 0;
         }
-        if (hipMemcpyAsync(d_list, h_list, live.size() * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(d_flags, h_flags, live.size() * n, hipMemcpyHostToDevice, s) != hipSuccess ||
-            rsmi::launch_gather_columns_masked(ga, d_list, d_flags, static_cast<uint32_t>(live.size()), d_cols, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(h_cols, d_cols, live.size() * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return RS_EDEVICE;
+        const uint32_t nlive = static_cast<uint32_t>(live.size());
+        hipError_t e = hipMemcpyAsync(d_list, h_list, nlive * sizeof(uint2), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && erased) e = hipMemcpyAsync(d_flags, h_flags, nlive * n, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = erased ? rsmi::launch_gather_columns_masked(ga, d_list, d_flags, nlive, d_cols, s)
+                       : rsmi::launch_gather_columns(ga, d_list, nlive, d_cols, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_cols, d_cols, nlive * n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return RS_EDEVICE;
         size_t kept = 0;
         reads.clear();
+        if (!erased) regen.assign(stripes * n, 0);
         for (size_t j = 0; j < live.size(); ++j) {
             const uint32_t i = live[j];
             uint8_t* kn = &known[static_cast<size_t>(i) * n];
@@ -1732,28 +1599,30 @@ int correct_degraded(rs_ctx* c, Lease& L, void* data, size_t dss, void* parity, 
                 give_up(i);
                 continue;
             }
-            for (size_t id = 0; id < n; ++id) {
-                if (!kn[id] || erased[static_cast<size_t>(i) * n + id]) continue;
-                uint8_t* slot = id < static_cast<size_t>(c->k)
-                                    ? static_cast<uint8_t*>(data) + i * dss + id * pitch
-                                    : static_cast<uint8_t*>(parity) + i * pss + (id - c->k) * pitch;
-                reads.push_back(rs_shard_read{i, static_cast<uint32_t>(id), 0u, slot});
-            }
+            if (!erased) std::copy(kn, kn + n, regen.begin() + static_cast<size_t>(i) * n);
+            for (size_t id = 0; erased && id < n; ++id)
+                if (kn[id] && !erased[static_cast<size_t>(i) * n + id])
+                    reads.push_back(rs_shard_read{i, static_cast<uint32_t>(id), 0u,
+                                                  reinterpret_cast<void*>(v.slot(i, id, c->k))});
             live[kept++] = i;
         }
         live.resize(kept);
         if (live.empty()) break;
-        // All of every live stripe's located set, in one batched read into place.
-        rc = rsmi::plan_reads(c->k, c->n, stripes, known.data(), span, reads.data(), reads.size(), &rp);
-        if (rc != RS_OK) return rc;
-        rsmi::ReadArgs ra = read_args(c, data, dss, parity, pss, pitch, len, rp.jobs.size());
-        if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
-        rc = read_stripes(c, L, data, dss, parity, pss, pitch, len, rp, ra, s, ReadFor::kScrub);
+        // All of every live stripe's located set, in one batched reconstruct
+        // or one batched read into place.
+        if (!erased) {
+            rc = reconstruct(c, L, v, stripes, regen.data(), nullptr, s);
+        } else {
+            rc = rsmi::plan_reads(c->k, c->n, stripes, known.data(), v.span(), reads.data(), reads.size(), &rp);
+            if (rc != RS_OK) return rc;
+            rsmi::ReadArgs ra = read_args(c, v, rp.jobs.size());
+            if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
+            rc = read_stripes(c, L, v, rp, ra, s, ReadFor::kScrub);
+        }
         if (rc != RS_OK) return rc;
         if (rewritten)
             for (uint32_t i : live)
-                for (size_t id = 0; id < n; ++id)
-                    rewritten[i * n + id] = known[i * n + id] && !erased[i * n + id] ? 1 : 0;
+                for (size_t x = i * n; x < (i + 1) * n; ++x) rewritten[x] = erased && erased[x] ? 0 : known[x];
         // Verify the live stripes again.
         rc = verify(live.data(), live.size());
         if (rc != RS_OK) return rc;
@@ -1779,6 +1648,13 @@ struct SetPick {
 rs_ctx* routed(rs_ctx* c, const void* p) {
     const int i = rsmi::set_route(c->set, p);
     return i < 0 ? nullptr : rsmi::set_member(c->set, i);
+}
+
+// A call on device memory at p: a device set's context becomes its member on
+// p's device (false: none); a single-device context stays.
+bool route(rs_ctx*& c, const void* p) {
+    if (c->set) c = routed(c, p);
+    return c != nullptr;
 }
 
 // Member i of c (c itself for a single-device context, i == 0).
@@ -1840,7 +1716,7 @@ int gpu_rows(rs_ctx* c, Lease& L, const std::vector<int>& surv, const std::vecto
             pat = L.d_onepat.p;
         }
         auto launch = [c, et, pat](uint8_t* din, uint8_t* dout, size_t pitch, size_t w, hipStream_t st) {
-            rsmi::MatArgs a = base_args(c, din, 0, dout, 0, pitch, w, 1);
+            rsmi::MatArgs a = base_args(c, StripeView{din, 0, dout, 0, pitch, w}, 1);
             set_patterns(c, 1, pat, a);
             a.stripe_desc = first_stripe_desc(c, pat);  // et outputs, not m
             return rsmi::launch_matmul(a, et, st);
@@ -1871,7 +1747,7 @@ bool encode_in_place(rs_ctx* c, Lease& L, const uint8_t* input, size_t S, uint8_
     // parity t at dout + t*S): no shard table to upload, one launch, and a
     // polled completion (rsmi::wait_event).
     (void)n;
-    rsmi::MatArgs a = base_args(c, reinterpret_cast<void*>(din), 0, reinterpret_cast<void*>(dout), 0, S, S, 1);
+    rsmi::MatArgs a = base_args(c, StripeView{reinterpret_cast<void*>(din), 0, reinterpret_cast<void*>(dout), 0, S, S}, 1);
     set_patterns(c, 1, c->d_encpat.p, a);
     a.stripe_desc = nullptr;
     hipError_t e = launch_encode(c, a, s);
@@ -2441,9 +2317,9 @@ int decode_launch(rs_ctx* c, Lease& L, const std::vector<uint8_t>& present, cons
     for (int ch = 0; ch < nch; ++ch) {
         const size_t off = chunk_off(S, ch, nch), w = chunk_off(S, ch + 1, nch) - off;
         rsmi::MatArgs& a = args[static_cast<size_t>(ch)];
-        a = strided ? base_args(c, reinterpret_cast<void*>(dev[0] + off), 0, reinterpret_cast<void*>(oalias + off), 0,
-                                span, w, 1)
-                    : base_args(c, nullptr, 0, nullptr, 0, span, w, 1);
+        a = base_args(c, strided ? StripeView{reinterpret_cast<void*>(dev[0] + off), 0,
+                                              reinterpret_cast<void*>(oalias + off), 0, span, w}
+                                 : StripeView::ptrs(span, w), 1);
         set_patterns(c, 1, pat, a);
         a.src = nullptr;                    // survivor j is id j, output t is id k + t
         a.desc0 = static_cast<uint32_t>(e);  // pattern 0, e outputs
@@ -2543,7 +2419,7 @@ bool encode_staged(rs_ctx* c, Lease& L, const uint8_t* input, size_t S, uint8_t*
     for (int ch = 0; ch < nch; ++ch) {
         const size_t off = chunk_off(S, ch, nch), w = chunk_off(S, ch + 1, nch) - off;
         rsmi::MatArgs& a = args[static_cast<size_t>(ch)];
-        a = base_args(c, static_cast<uint8_t*>(din) + off, 0, static_cast<uint8_t*>(dout) + off, 0, span, w, 1);
+        a = base_args(c, StripeView{static_cast<uint8_t*>(din) + off, 0, static_cast<uint8_t*>(dout) + off, 0, span, w}, 1);
         set_patterns(c, 1, c->d_encpat.p, a);
         a.stripe_desc = nullptr;
     }
@@ -3060,7 +2936,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 6) return rsmi::combine_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 7) return rsmi::update_degraded_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
-    if (which == 1 && use_bitslice_rec(c)) return c->rec_name.c_str();
+    if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
 }
 
@@ -3221,15 +3097,13 @@ int rs_encode_stripes(rs_ctx* c, const void* data, size_t dss, void* parity, siz
                       size_t pitch, size_t len, size_t stripes, void* stream) {
     if (!c) return RS_EINVAL;
     if (c->m == 0 || stripes == 0 || len == 0) return RS_OK;
-    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_encode_stripes(mc, data, dss, parity, pss, pitch, len, stripes, stream) : RS_EINVAL;
-    }
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (!check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, data)) return RS_EINVAL;
     // Reads only state that is immutable after rs_new: no lock, no lease.
     DeviceGuard g(c->device);
     if (!g.ok) return RS_EDEVICE;
-    rsmi::MatArgs a = base_args(c, const_cast<void*>(data), dss, parity, pss, pitch, len, stripes);
+    rsmi::MatArgs a = base_args(c, v, stripes);
     set_patterns(c, 1, c->d_encpat.p, a);
     a.stripe_desc = nullptr;
     return hip_status(launch_encode(c, a, static_cast<hipStream_t>(stream)));
@@ -3240,17 +3114,12 @@ int rs_reconstruct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size
                            void* stream) {
     if (!c || !erased) return RS_EINVAL;
     if (stripes == 0 || len == 0) return RS_OK;
-    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_reconstruct_stripes(mc, data, dss, parity, pss, pitch, len, stripes, erased, stream) : RS_EINVAL;
-    }
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return reconstruct(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, erased, nullptr,
-                       static_cast<hipStream_t>(stream));
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (!check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, data)) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return reconstruct(c, *sc.L, v, stripes, erased, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int rs_verify_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
@@ -3258,38 +3127,29 @@ int rs_verify_stripes(rs_ctx* c, const void* data, size_t dss, const void* parit
     if (!c) return RS_EINVAL;
     if (stripes == 0 || len == 0) return RS_OK;
     if (!first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
-    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, c->m > 0 ? data : first_bad);
-        return mc ? rs_verify_stripes(mc, data, dss, parity, pss, pitch, len, stripes, first_bad, stream) : RS_EINVAL;
-    }
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, c->m > 0 ? data : first_bad)) return RS_EINVAL;
     // Reads only state that is immutable after rs_new: no lock, no lease.
     DeviceGuard g(c->device);
     if (!g.ok) return RS_EDEVICE;
-    return launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, first_bad,
-                                 static_cast<hipStream_t>(stream));
+    return launch_verify_stripes(c, v, stripes, nullptr, stripes, first_bad, static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
                        size_t stripes, int* status, uint8_t* rewritten, void* stream) {
     if (!c) return RS_EINVAL;
     if (stripes == 0 || len == 0) return RS_OK;
-    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
     if (c->m > 0 && stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
-    if (c->set && c->m > 0) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_correct_stripes(mc, data, dss, parity, pss, pitch, len, stripes, status, rewritten, stream)
-                  : RS_EINVAL;
-    }
+    if (c->m > 0 && !route(c, data)) return RS_EINVAL;
     if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
     if (rewritten) std::memset(rewritten, 0, stripes * static_cast<size_t>(c->n));
     if (c->m == 0) return RS_OK;  // no parity: every stripe is a codeword
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return correct_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, status, rewritten,
-                           static_cast<hipStream_t>(stream));
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return scrub_stripes(c, *sc.L, v, stripes, nullptr, status, rewritten, static_cast<hipStream_t>(stream));
 }
 
 int rs_verify_degraded(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
@@ -3297,27 +3157,21 @@ int rs_verify_degraded(rs_ctx* c, const void* data, size_t dss, const void* pari
     if (!c) return RS_EINVAL;
     if (stripes == 0 || len == 0) return RS_OK;
     if (!erased || !first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
-    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, c->m > 0 ? data : first_bad);
-        return mc ? rs_verify_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, first_bad, stream)
-                  : RS_EINVAL;
-    }
-    const rsmi::CheckLayout lay{reinterpret_cast<uintptr_t>(data), reinterpret_cast<uintptr_t>(parity), dss, pss,
-                                pitch};
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, c->m > 0 ? data : first_bad)) return RS_EINVAL;
     rsmi::CheckPlan plan;
-    const int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, nullptr, 0, lay, &plan);
+    const int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, nullptr, 0, check_layout(v), &plan);
     if (rc != RS_OK) return rc;
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
     // No flag set: rs_verify_stripes' launch, without a lock or a lease.
-    if (plan.intact.size() == stripes)
-        return launch_verify_stripes(c, data, dss, parity, pss, pitch, len, stripes, nullptr, stripes, first_bad,
-                                     static_cast<hipStream_t>(stream));
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return check_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, plan, first_bad,
-                         static_cast<hipStream_t>(stream));
+    if (plan.intact.size() == stripes) {
+        DeviceGuard g(c->device);
+        if (!g.ok) return RS_EDEVICE;
+        return launch_verify_stripes(c, v, stripes, nullptr, stripes, first_bad, static_cast<hipStream_t>(stream));
+    }
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return check_stripes(c, *sc.L, v, stripes, plan, first_bad, static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
@@ -3325,14 +3179,10 @@ int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t 
     if (!c) return RS_EINVAL;
     if (stripes == 0 || len == 0) return RS_OK;
     if (!erased) return RS_EINVAL;
-    if (c->m > 0 && !check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
     if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
-    if (c->set && c->m > 0) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_correct_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, status, rewritten,
-                                        stream)
-                  : RS_EINVAL;
-    }
+    if (c->m > 0 && !route(c, data)) return RS_EINVAL;
     // The erasure counts are checked before anything is written or launched.
     bool degraded = false;
     const size_t n = static_cast<size_t>(c->n);
@@ -3345,12 +3195,9 @@ int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t 
     if (!degraded) return rs_correct_stripes(c, data, dss, parity, pss, pitch, len, stripes, status, rewritten, stream);
     if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
     if (rewritten) std::memset(rewritten, 0, stripes * n);
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return correct_degraded(c, *lg.L, data, dss, parity, pss, pitch, len, stripes, erased, status, rewritten,
-                            static_cast<hipStream_t>(stream));
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return scrub_stripes(c, *sc.L, v, stripes, erased, status, rewritten, static_cast<hipStream_t>(stream));
 }
 
 int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
@@ -3358,30 +3205,20 @@ int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t ps
     if (!c) return RS_EINVAL;
     if (count == 0 || stripes == 0 || len == 0) return RS_OK;
     if (!updates) return RS_EINVAL;
-    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_update_stripes(mc, data, dss, parity, pss, pitch, len, stripes, updates, count, stream)
-                  : RS_EINVAL;
-    }
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (!check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, data)) return RS_EINVAL;
     rsmi::UpdatePlan plan;
     const int rc = rsmi::plan_updates(c->k, stripes, updates, count, &plan);
     if (rc != RS_OK) return rc;
     // No src may lie in the call's data or parity region: a block would read
     // as "new" what another block is overwriting.
-    const size_t span = round_up(len, 16);
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
-    const uintptr_t d1 = d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span;
-    const uintptr_t p1 = c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0;
-    for (const rsmi::UpdateEntry& e : plan.entries) {
-        const uintptr_t s0 = static_cast<uintptr_t>(e.src), s1 = s0 + span;
-        if ((s0 < d1 && d0 < s1) || (s0 < p1 && p0 < s1)) return RS_EINVAL;
-    }
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return update_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
+    const rsmi::UpdateExtent ext = v.extent(stripes, c->k, c->m);
+    for (const rsmi::UpdateEntry& e : plan.entries)
+        if (touches(ext, static_cast<uintptr_t>(e.src))) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return update_stripes(c, *sc.L, v, plan, static_cast<hipStream_t>(stream));
 }
 
 int rs_update_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
@@ -3390,20 +3227,13 @@ int rs_update_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t p
     if (!c) return RS_EINVAL;
     if (count == 0 || stripes == 0 || len == 0) return RS_OK;
     if (!updates || !erased) return RS_EINVAL;
-    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_update_degraded(mc, data, dss, parity, pss, pitch, len, stripes, erased, updates, count, stream)
-                  : RS_EINVAL;
-    }
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (!check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, data)) return RS_EINVAL;
     // No src may lie in the call's data or parity region (rs_update_stripes):
     // a defect of the list, so the planner looks for it before it counts any
     // stripe's erasures.
-    const size_t span = round_up(len, 16);
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
-    const rsmi::UpdateExtent ext{
-        d0, d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span, p0,
-        c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0, span};
+    const rsmi::UpdateExtent ext = v.extent(stripes, c->k, c->m);
     rsmi::UpdateDegradedPlan plan;
     const int rc = rsmi::plan_update_degraded(c->k, c->n, stripes, erased, updates, count, &ext, &plan);
     if (rc != RS_OK) return rc;
@@ -3412,11 +3242,9 @@ int rs_update_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t p
     // refused) and only the data is overwritten.
     if (!plan.degraded || c->m == 0)
         return rs_update_stripes(c, data, dss, parity, pss, pitch, len, stripes, updates, count, stream);
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return update_degraded(c, *lg.L, data, dss, parity, pss, pitch, len, plan, static_cast<hipStream_t>(stream));
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return update_degraded(c, *sc.L, v, plan, static_cast<hipStream_t>(stream));
 }
 
 int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch, size_t len,
@@ -3424,35 +3252,24 @@ int rs_read_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity,
     if (!c) return RS_EINVAL;
     if (count == 0 || stripes == 0 || len == 0) return RS_OK;
     if (!erased || !reads) return RS_EINVAL;
-    if (!check_stripes_args(c, data, dss, parity, pss, pitch, len)) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, data);
-        return mc ? rs_read_stripes(mc, data, dss, parity, pss, pitch, len, stripes, erased, reads, count, stream)
-                  : RS_EINVAL;
-    }
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (!check_stripes_args(c, v)) return RS_EINVAL;
+    if (!route(c, data)) return RS_EINVAL;
     // No dst may lie in the call's data or parity region: the stripes are
     // only read.  A defect of the list, so looked for before the planner
     // counts any stripe's erasures.
-    const size_t span = round_up(len, 16);
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
-    const uintptr_t d1 = d0 + (stripes - 1) * dss + static_cast<size_t>(c->k - 1) * pitch + span;
-    const uintptr_t p1 = c->m > 0 ? p0 + (stripes - 1) * pss + static_cast<size_t>(c->m - 1) * pitch + span : p0;
-    for (size_t i = 0; i < count; ++i) {
-        const uintptr_t t0 = reinterpret_cast<uintptr_t>(reads[i].dst), t1 = t0 + span;
-        if ((t0 < d1 && d0 < t1) || (t0 < p1 && p0 < t1)) return RS_EINVAL;
-    }
+    const rsmi::UpdateExtent ext = v.extent(stripes, c->k, c->m);
+    for (size_t i = 0; i < count; ++i)
+        if (touches(ext, reinterpret_cast<uintptr_t>(reads[i].dst))) return RS_EINVAL;
     rsmi::ReadPlan plan;
-    const int rc = rsmi::plan_reads(c->k, c->n, stripes, erased, span, reads, count, &plan);
+    const int rc = rsmi::plan_reads(c->k, c->n, stripes, erased, v.span(), reads, count, &plan);
     if (rc != RS_OK) return rc;
-    rsmi::ReadArgs a = read_args(c, data, dss, parity, pss, pitch, len, plan.jobs.size());
+    rsmi::ReadArgs a = read_args(c, v, plan.jobs.size());
     if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
-    // launch_copy_pieces: a block per (piece, 4 KiB chunk)
-    if (plan.copies.size() * ((static_cast<uint64_t>(a.ncols16) + 255) / 256) > 0x7FFFFFFFull) return RS_EINVAL;
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return read_stripes(c, *lg.L, data, dss, parity, pss, pitch, len, plan, a, static_cast<hipStream_t>(stream));
+    if (!copy_pieces_fit(plan.copies.size(), a.ncols16)) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return read_stripes(c, *sc.L, v, plan, a, static_cast<hipStream_t>(stream));
 }
 
 int rs_combine(rs_ctx* c, const rs_combine_job* jobs, size_t count, size_t len, void* stream) {
@@ -3461,20 +3278,16 @@ int rs_combine(rs_ctx* c, const rs_combine_job* jobs, size_t count, size_t len, 
     rsmi::CombinePlan plan;
     const int rc = rsmi::plan_combine(jobs, count, len, &plan);
     if (rc != RS_OK) return rc;
-    if (c->set) {  // the member on the device of the first destination
-        c = routed(c, reinterpret_cast<const void*>(static_cast<uintptr_t>(plan.addrs[plan.jobs[0].nsrc])));
-        if (!c) return RS_EINVAL;
-    }
+    // A device set: the member on the device of the first destination.
+    if (!route(c, reinterpret_cast<const void*>(static_cast<uintptr_t>(plan.addrs[plan.jobs[0].nsrc])))) return RS_EINVAL;
     rsmi::CombArgs a{};
     a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
     a.njobs = static_cast<uint32_t>(plan.jobs.size());
     a.xcd = c->xcd_update;
     if (!rsmi::plan_combine_launch(&a, plan.max_nsrc, plan.max_nout)) return RS_EINVAL;
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return combine(c, *lg.L, plan, a, static_cast<hipStream_t>(stream));
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return combine(c, *sc.L, plan, a, static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
@@ -3483,15 +3296,10 @@ int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_
     if (stripes == 0 || len == 0) return RS_OK;
     if (round_up(len, 16) / 16 >= (size_t(1) << 28)) return RS_EINVAL;  // 32-bit column offsets
     if (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u) return RS_EINVAL;
-    if (c->set) {
-        rs_ctx* mc = routed(c, shard_ptrs);
-        return mc ? rs_reconstruct_ptrs(mc, shard_ptrs, len, stripes, erased, stream) : RS_EINVAL;
-    }
-    DeviceGuard g(c->device);
-    if (!g.ok) return RS_EDEVICE;
-    LeaseGuard lg(c);
-    if (!lg.L) return RS_ENOMEM;
-    return reconstruct(c, *lg.L, nullptr, 0, nullptr, 0, round_up(len, 16), len, stripes, erased, shard_ptrs,
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return reconstruct(c, *sc.L, StripeView::ptrs(round_up(len, 16), len), stripes, erased, shard_ptrs,
                        static_cast<hipStream_t>(stream));
 }
 
@@ -3524,7 +3332,7 @@ int rs_encode(rs_ctx* c, const uint8_t* input, size_t len, uint8_t* parity) {
     for (int j = 0; j < c->k; ++j) srcs[j] = input + static_cast<size_t>(j) * S;
     for (int t = 0; t < c->m; ++t) dsts[t] = parity + static_cast<size_t>(t) * S;
     auto launch = [c](uint8_t* din, uint8_t* dout, size_t pitch, size_t w, hipStream_t st) {
-        rsmi::MatArgs a = base_args(c, din, 0, dout, 0, pitch, w, 1);
+        rsmi::MatArgs a = base_args(c, StripeView{din, 0, dout, 0, pitch, w}, 1);
         set_patterns(c, 1, c->d_encpat.p, a);
         return launch_encode(c, a, st);
     };
@@ -3881,7 +3689,7 @@ int rs_decode_batch(rs_ctx* c, int batch, const int* counts, int* numbers, const
                 if (!in_place)
                     pipe->copy(std::vector<rsmi::CopyPool::Piece>(stage_in.begin() + j0 * k, stage_in.begin() + j1 * k));
                 rsmi::trace_mark(kStage[ch]);
-                const int st = reconstruct(c, L, nullptr, 0, nullptr, 0, sp, S, j1 - j0, erased.data() + j0 * n,
+                const int st = reconstruct(c, L, StripeView::ptrs(sp, S), j1 - j0, erased.data() + j0 * n,
                                            static_cast<const uint64_t*>(L.d_pieces.p) + j0 * n, s);
                 if (st != RS_OK || hipEventRecord(L.ev[ch], s) != hipSuccess) return finish(st != RS_OK ? st : RS_EDEVICE);
                 rsmi::trace_mark(kLaunch[ch]);
@@ -3950,7 +3758,7 @@ int rs_decode_batch(rs_ctx* c, int batch, const int* counts, int* numbers, const
                 hipSuccess)
                 return finish(RS_EDEVICE);
         }
-        const int st = reconstruct(c, L, nullptr, 0, nullptr, 0, pitch, S, B, erased.data(),
+        const int st = reconstruct(c, L, StripeView::ptrs(pitch, S), B, erased.data(),
                                    static_cast<const uint64_t*>(L.d_pieces.p), s);
         if (st != RS_OK) return finish(st);
         // Regenerated data shards out, in chunks with an event each, so the host
@@ -4071,7 +3879,7 @@ int rs_encode_batch(rs_ctx* c, int batch, const uint8_t* const* inputs, size_t l
                     in.push_back({h_in + (j * k + i) * pitch, inputs[todo[g0 + j]] + i * S, S, true});
             pipe->copy(in);
             rsmi::trace_mark(ch == 0 ? "stage0" : ch == 1 ? "stage1" : ch == 2 ? "stage2" : "stage3");
-            rsmi::MatArgs a = base_args(c, d_in + j0 * k * pitch, k * pitch, d_out + j0 * m * pitch, m * pitch, pitch, S,
+            rsmi::MatArgs a = base_args(c, StripeView{d_in + j0 * k * pitch, k * pitch, d_out + j0 * m * pitch, m * pitch, pitch, S},
                                         j1 - j0);
             set_patterns(c, 1, c->d_encpat.p, a);
             a.stripe_desc = nullptr;
