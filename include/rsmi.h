@@ -79,7 +79,8 @@ const char *rs_strerror(int status);
  * the rs_combine variant that serves a narrow job of this code's shape (nsrc
  * = k, nout = min(m, 4), or 1 when m is 0), e.g. "combine_MG4_B256"; which =
  * 7: the rs_update_degraded variant, e.g. "update_degraded_MG4_B256" (no
- * reference counterpart). */
+ * reference counterpart); which = 8: the rs_correct_columns variant, e.g.
+ * "columns_MG4_B256", or "none" for a code the call does not serve. */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -240,6 +241,57 @@ int rs_correct_degraded(rs_ctx *ctx, void *data, size_t data_stripe_stride, void
                         size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
                         size_t stripes, const uint8_t *erased, int *status,
                         uint8_t *rewritten, void *stream);
+
+/* Column scrub: infectious Correct, stripe-batched -- every byte column of
+ * every stripe decoded on its own (Berlekamp-Welch's result, column by column).
+ * Layout and alignment rules as rs_encode_stripes; erased (HOST, stripes * n
+ * flags as for rs_reconstruct_stripes, not retained) may be NULL: nothing is
+ * missing.  The slots of erased shards are never dereferenced.
+ *
+ * For stripe s and byte offset o < shard_len, with P the present shards of s,
+ * r = |P| and y their r bytes at o:
+ *  - y lies on a codeword of the code punctured to P: nothing is written;
+ *  - else a codeword lies within Hamming distance floor((r - k) / 2) of y: it
+ *    is unique, and exactly the bytes that differ from it are overwritten with
+ *    its values;
+ *  - else nothing in that column is written and stripe s ends
+ *    RS_ETOO_MANY_ERRORS.  Beyond the radius the decoder may, like
+ *    Berlekamp-Welch, land on another codeword.
+ * The columns of a stripe do not depend on each other: a stripe with one
+ * hopeless column still gets every other column repaired, and a later
+ * rs_verify_stripes / rs_verify_degraded reports the first hopeless column as
+ * first_bad.  So the call repairs any stripe in which each COLUMN has at most
+ * floor((r - k) / 2) wrong shares, however many shards are touched overall --
+ * three bad sectors on three devices at three offsets of an RS(10,4) stripe --
+ * where rs_correct_stripes / rs_correct_degraded need at most that many wrong
+ * SHARDS.  On scattered damage call it before or instead of them: the
+ * shard-level scrub regenerates a located shard from survivors that may be
+ * wrong at other columns, which spreads the damage.
+ *
+ * status (HOST, int[stripes], may be NULL): RS_OK or RS_ETOO_MANY_ERRORS.
+ * corrected (HOST, uint32_t[stripes*n], may be NULL): corrected[s*n + i] = the
+ * bytes of shard i of stripe s that the call changed; 0 for erased shards and
+ * clean stripes.
+ * Never read for comparison and never written: the slots of erased shards,
+ * bytes at offsets >= shard_len (the pad to 16, pitch gaps), stride gaps,
+ * clean stripes.  A wrong byte inside [shard_len, round_up(shard_len, 16)) is
+ * not an error.
+ * Refuses what rs_correct_degraded refuses, with the same codes: more than m
+ * erasures in any stripe -> RS_ENOT_ENOUGH, nothing launched or written.  An
+ * inconsistent stripe with r - k < 2 ends RS_ETOO_MANY_ERRORS unwritten; a
+ * stripe with r == k is RS_OK.  stripes == 0, shard_len == 0 or m == 0: RS_OK.
+ * Codes with m > 16 -> RS_EINVAL (the kernel keeps at most 16 syndromes per
+ * column); every (k, n) with 1 <= m <= 16 is served, up to n = 256.
+ * Synchronous like rs_correct_stripes: verify, one column launch over the
+ * inconsistent stripes only (a call on clean stripes launches nothing more
+ * than the verify), verify of those stripes again.  Returns RS_OK if every
+ * stripe ends consistent, else RS_ETOO_MANY_ERRORS. */
+int rs_correct_columns(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                       size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                       size_t stripes, const uint8_t *erased /* HOST, stripes*n, may be NULL */,
+                       int *status /* HOST int[stripes], may be NULL */,
+                       uint32_t *corrected /* HOST uint32[stripes*n], may be NULL */,
+                       void *stream);
 
 /* In-place parity update: overwrite data shards of stripes that already hold
  * parity and patch that parity from the difference alone.  Layout and
@@ -481,6 +533,8 @@ enum {
     RS_STAT_COMBINE_ROWS = 19,     /* output rows written by rs_combine                */
     RS_STAT_UPDATE_DEGRADED = 20,  /* stripes patched by the rs_update_degraded kernel */
     RS_STAT_UPDATE_ABSORBED = 21,  /* erased changed shards rs_update_degraded took into the parity only */
+    RS_STAT_COLUMN_STRIPES = 22,   /* inconsistent stripes rs_correct_columns handed to the column kernel */
+    RS_STAT_COLUMN_BYTES = 23,     /* bytes rs_correct_columns corrected                */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -591,7 +645,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    members at once; per-message status and the return value as on one GPU;
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
- *    rs_verify_degraded, rs_correct_degraded, rs_update_degraded, rs_reconstruct_ptrs,
+ *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -30,6 +31,8 @@
 #include "bitslice.hpp"
 #include "blake2b.hpp"
 #include "check_plan.hpp"
+#include "column_correct.hpp"
+#include "column_decode.hpp"
 #include "combine_plan.hpp"
 #include "device_set.hpp"
 #include "gf256.hpp"
@@ -229,7 +232,7 @@ struct Lease {
     Staging st_onepat;                 // host-API decode: the one-pattern table, read in place by the kernel
     Staging st_out;                    // decode_in_place: regenerated shares when dst is not engine-pinned
     Staging st_in;                     // decode_staged / encode_staged: a small message's survivors
-    Staging st_scrub;                  // rs_correct_stripes: verdicts, stripe list, gathered columns
+    Staging st_scrub;                  // rs_correct_stripes: verdicts, stripe list, gathered columns; rs_correct_columns
     // Mailbox grid of a staged single message (MailboxCall): the job board
     // in pinned coherent memory, its device alias and the grid's device
     // words; allocated on first use.
@@ -371,6 +374,7 @@ struct rs_ctx {
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
     std::atomic<int64_t> update_degraded{0}, update_absorbed{0};         // rs_update_degraded (rs_stat)
+    std::atomic<int64_t> column_stripes{0}, column_bytes{0};             // rs_correct_columns (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1632,6 +1636,143 @@ int scrub_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, cons
         live.resize(kept);
     }
     for (uint32_t i : live) give_up(i);  // still inconsistent after m rounds
+    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+}
+
+// --------------------------------------------------------- column scrub ----
+// rs_correct_columns on stream s with lease L (1 <= m <= 16; erased may be
+// nullptr).  Device workspace (L.d_scrub) and its pinned mirror (L.st_scrub):
+//   first_bad u32 [stripes] | list uint2 [stripes]
+// for the verifies, as scrub_stripes, and once the first verify has named the
+// nd inconsistent stripes with r - k >= 2 and their npat distinct erasure sets,
+//   | jobs uint4 [nd] | tables [npat][column_table_bytes(n)] | counts u32 [nd * n] | fail u32 [nd]
+// behind them: the jobs and tables go up in one copy, the counts and fail
+// words come back in one.  Two host round trips: the verdicts, then the
+// counters together with the final verify's verdicts of the same stripes.
+int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint8_t* erased, int* status,
+                    uint32_t* corrected, hipStream_t s) {
+    const size_t n = static_cast<size_t>(c->n);
+    const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
+    const size_t jobs_off = round_up(list_off + stripes * sizeof(uint2), 16);
+    L.begin(s);
+    if (!L.st_scrub.acquire(jobs_off) || !L.d_scrub.reserve_on(jobs_off, s)) return RS_ENOMEM;
+    uint8_t* hb = static_cast<uint8_t*>(L.st_scrub.p);
+    uint8_t* db = static_cast<uint8_t*>(L.d_scrub.p);
+    // Every exit records the lease's last device use.
+    struct End {
+        Lease& L;
+        hipStream_t s;
+        ~End() { L.end(s); }
+    } end_guard{L, s};
+
+    rsmi::CheckPlan cp;
+    // Verify of all stripes (list == nullptr) or the listed ones on s; the
+    // verdicts are at db afterwards.
+    auto verify = [&](const uint32_t* list, size_t count) -> int {
+        if (erased) {
+            const int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), &cp);
+            return rc != RS_OK ? rc : check_stripes(c, L, v, stripes, cp, reinterpret_cast<uint32_t*>(db), s);
+        }
+        uint2* h_list = reinterpret_cast<uint2*>(hb + list_off);
+        uint2* d_list = reinterpret_cast<uint2*>(db + list_off);
+        for (size_t j = 0; j < count; ++j) h_list[j] = make_uint2(list[j], static_cast<uint32_t>(c->m));
+        if (list && hipMemcpyAsync(d_list, h_list, count * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
+            return RS_EDEVICE;
+        return launch_verify_stripes(c, v, stripes, list ? d_list : nullptr, list ? count : stripes,
+                                     reinterpret_cast<uint32_t*>(db), s);
+    };
+    int rc = verify(nullptr, 0);
+    if (rc != RS_OK) return rc;
+    if (hipMemcpyAsync(hb, db, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return RS_EDEVICE;
+
+    bool failed = false;
+    auto give_up = [&](uint32_t i) {
+        if (status) status[i] = RS_ETOO_MANY_ERRORS;
+        failed = true;
+    };
+    // The inconsistent stripes that have a radius, and their erasure sets'
+    // tables (one per distinct set).
+    std::vector<uint32_t> dirty;
+    std::vector<uint4> jobs;
+    std::map<std::vector<uint8_t>, uint32_t> sets;
+    std::vector<uint8_t> flags(n, 0);
+    const uint32_t* h_fb = reinterpret_cast<const uint32_t*>(hb);
+    for (size_t i = 0; i < stripes; ++i) {
+        if (h_fb[i] == RS_VERIFY_CLEAN) continue;
+        int r = c->n;
+        for (size_t id = 0; erased && id < n; ++id) {
+            flags[id] = erased[i * n + id] != 0 ? 1 : 0;
+            r -= flags[id];
+        }
+        if (r - c->k < 2) {
+            give_up(static_cast<uint32_t>(i));
+            continue;
+        }
+        const uint32_t pat = sets.emplace(flags, static_cast<uint32_t>(sets.size())).first->second;
+        dirty.push_back(static_cast<uint32_t>(i));
+        jobs.push_back(make_uint4(static_cast<uint32_t>(i), pat, static_cast<uint32_t>(r), static_cast<uint32_t>(r - c->k)));
+    }
+    const size_t nd = dirty.size();
+    if (nd == 0) return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+
+    rsmi::ColArgs a{};
+    a.data = static_cast<uint8_t*>(v.data);
+    a.parity = static_cast<uint8_t*>(v.parity);
+    a.data_ss = v.dss;
+    a.parity_ss = v.pss;
+    a.pitch = v.pitch;
+    a.ncols16 = v.ncols16();
+    a.shard_len = static_cast<uint32_t>(v.len);
+    a.k = static_cast<uint32_t>(c->k);
+    a.n = static_cast<uint32_t>(c->n);
+    a.njobs = static_cast<uint32_t>(nd);
+    if (!rsmi::plan_column_correct(&a)) return RS_EINVAL;
+
+    const size_t tb = rsmi::column_table_bytes(c->n);
+    const size_t tab_off = jobs_off + nd * sizeof(uint4);
+    const size_t cnt_off = tab_off + sets.size() * tb;
+    const size_t fail_off = cnt_off + nd * n * sizeof(uint32_t);
+    const size_t bytes = fail_off + nd * sizeof(uint32_t);
+    // Growing the workspace drops the verdicts, which the host is done with.
+    if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
+    hb = static_cast<uint8_t*>(L.st_scrub.p);
+    db = static_cast<uint8_t*>(L.d_scrub.p);
+    std::memcpy(hb + jobs_off, jobs.data(), nd * sizeof(uint4));
+    for (const auto& set : sets) rsmi::column_tables(c->n, set.first.data(), hb + tab_off + set.second * tb);
+    a.jobs = reinterpret_cast<const uint4*>(db + jobs_off);
+    a.tables = db + tab_off;
+    a.gf = dev_enc(c) + n * static_cast<size_t>(c->k);
+    a.counts = reinterpret_cast<uint32_t*>(db + cnt_off);
+    a.fail = reinterpret_cast<uint32_t*>(db + fail_off);
+    hipError_t e = hipMemcpyAsync(db + jobs_off, hb + jobs_off, cnt_off - jobs_off, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(db + cnt_off, 0, bytes - cnt_off, s);
+    if (e == hipSuccess) e = rsmi::launch_column_correct(a, c->m, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hb + cnt_off, db + cnt_off, bytes - cnt_off, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return RS_EDEVICE;
+    c->column_stripes += static_cast<int64_t>(nd);
+
+    // The same stripes again: one still inconsistent has a hopeless column,
+    // whatever its fail word says.
+    rc = verify(dirty.data(), nd);
+    if (rc != RS_OK) return rc;
+    if (hipMemcpyAsync(hb, db, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return RS_EDEVICE;
+    h_fb = reinterpret_cast<const uint32_t*>(hb);
+    const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(hb + cnt_off);
+    const uint32_t* h_fail = reinterpret_cast<const uint32_t*>(hb + fail_off);
+    int64_t changed = 0;
+    for (size_t j = 0; j < nd; ++j) {
+        const uint32_t i = dirty[j];
+        for (size_t id = 0; id < n; ++id) {
+            changed += h_cnt[j * n + id];
+            if (corrected) corrected[i * n + id] = h_cnt[j * n + id];
+        }
+        if (h_fail[j] != 0 || h_fb[i] != RS_VERIFY_CLEAN) give_up(i);
+    }
+    c->column_bytes += changed;
     return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
 }
 
@@ -2935,6 +3076,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 5) return rsmi::check_variant_name(c->k);
     if (which == 6) return rsmi::combine_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 7) return rsmi::update_degraded_variant_name(c->m);
+    if (which == 8) return rsmi::column_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -2995,6 +3137,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_COMBINE_ROWS: return c->combine_rows.load();
         case RS_STAT_UPDATE_DEGRADED: return c->update_degraded.load();
         case RS_STAT_UPDATE_ABSORBED: return c->update_absorbed.load();
+        case RS_STAT_COLUMN_STRIPES: return c->column_stripes.load();
+        case RS_STAT_COLUMN_BYTES: return c->column_bytes.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3198,6 +3342,33 @@ int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t 
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
     return scrub_stripes(c, *sc.L, v, stripes, erased, status, rewritten, static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_columns(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                       size_t stripes, const uint8_t* erased, int* status, uint32_t* corrected, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the job list
+    if (c->m > rsmi::kColumnMaxSyn) return RS_EINVAL;  // the kernel keeps at most 16 syndromes per column
+    if (c->m > 0 && !route(c, data)) return RS_EINVAL;
+    // The erasure counts are checked before anything is written or launched.
+    const size_t n = static_cast<size_t>(c->n);
+    bool degraded = false;
+    for (size_t i = 0; erased && i < stripes; ++i) {
+        int e = 0;
+        for (size_t id = 0; id < n; ++id) e += erased[i * n + id] != 0;
+        if (e > c->m) return RS_ENOT_ENOUGH;
+        degraded |= e > 0;
+    }
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (corrected) std::fill(corrected, corrected + stripes * n, 0u);
+    if (c->m == 0) return RS_OK;  // no parity: every stripe is a codeword
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return correct_columns(c, *sc.L, v, stripes, degraded ? erased : nullptr, status, corrected,
+                           static_cast<hipStream_t>(stream));
 }
 
 int rs_update_stripes(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,

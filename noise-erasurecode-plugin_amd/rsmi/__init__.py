@@ -39,7 +39,8 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
-    "rs_verify_degraded", "rs_correct_degraded", "rs_update_degraded", "rs_combine", "rs_pattern_survivors",
+    "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
+    "rs_pattern_survivors",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
     "rs_pattern_rows",
@@ -163,6 +164,7 @@ def _lib() -> ctypes.CDLL:
             "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_verify_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
+            "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
             "rs_pattern_survivors": (i32, [vp, vp, ctypes.POINTER(i32)]),
             "rs_pattern_count": (i32, [vp]),
@@ -331,7 +333,8 @@ class FEC:
 
     def kernel_name(self, which: int = 0) -> str:
         """Kernel serving encode (0), reconstruct (1), verify (2), update
-        (3), degraded read (4) or degraded check (5): diagnostics."""
+        (3), degraded read (4), degraded check (5), combine (6), degraded
+        update (7) or column scrub (8): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -517,6 +520,31 @@ class FEC:
             _check(rc, "rs_correct_degraded")
         return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
 
+    def correct_columns(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                        pitch: int, shard_len: int, stripes: int, erased: Optional[bytes] = None,
+                        stream: int = 0):
+        """rs_correct_columns (column scrub): every byte column of every
+        stripe decoded on its own, so a stripe is repaired whenever each
+        column has at most (r - k) // 2 wrong shares among its r present
+        ones.  Returns (status, corrected): status[s] is RS_OK or
+        RS_ETOO_MANY_ERRORS, corrected[s * n + i] the bytes of shard i of
+        stripe s the call changed.  erased: stripes * n flags, or None.
+        Raises only for argument, device or memory errors and for more than
+        m erasures."""
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        st = (ctypes.c_int * max(stripes, 1))()
+        cnt = (ctypes.c_uint32 * max(stripes * self.n, 1))()
+        rc = _lib().rs_correct_columns(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                       pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), st,
+                                       ctypes.cast(cnt, ctypes.c_void_p), stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_columns")
+        return [st[s] for s in range(stripes)], [cnt[x] for x in range(stripes * self.n)]
+
     def update_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
                        pitch: int, shard_len: int, stripes: int, updates: Sequence[tuple],
                        stream: int = 0) -> None:
@@ -606,7 +634,7 @@ class FEC:
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
-     STAT_UPDATE_ABSORBED) = range(22)
+     STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES) = range(24)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
