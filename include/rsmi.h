@@ -80,7 +80,9 @@ const char *rs_strerror(int status);
  * = k, nout = min(m, 4), or 1 when m is 0), e.g. "combine_MG4_B256"; which =
  * 7: the rs_update_degraded variant, e.g. "update_degraded_MG4_B256" (no
  * reference counterpart); which = 8: the rs_correct_columns variant, e.g.
- * "columns_MG4_B256", or "none" for a code the call does not serve. */
+ * "columns_MG4_B256", or "none" for a code the call does not serve; which =
+ * 9: the per-job-length twin of which = 6 that serves rs_combine_lens calls of
+ * mixed lengths, e.g. "combine_lens_MG4_B256". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -143,6 +145,49 @@ int rs_decode_batch(rs_ctx *ctx, int batch, const int *counts, int *numbers,
  * returns RS_OK if every message encoded, else the first failing status. */
 int rs_encode_batch(rs_ctx *ctx, int batch, const uint8_t *const *inputs, size_t len,
                     uint8_t *const *parities, int *status);
+
+/* rs_encode_batch_lens / rs_decode_batch_lens: rs_encode_batch /
+ * rs_decode_batch for messages of different lengths -- message b has
+ * lens[b] input bytes / share_lens[b] bytes per share (HOST arrays of `batch`
+ * entries, not retained), and everything else is as in those calls, message
+ * by message: every message's output is bit-identical to what rs_encode /
+ * rs_decode gives for it alone.  Real traffic does not come in equal lengths;
+ * with these calls it is batched all the same.
+ * Encode: lens[b] % k != 0 fails that message alone with
+ * RS_ELEN_NOT_MULTIPLE, a NULL input or parity with a non-zero length fails
+ * it alone with RS_EINVAL; a length of 0, or m == 0, is RS_OK with nothing
+ * written.
+ * Decode: validation, the in-place sort of each message's slice of numbers /
+ * shares, the error codes and the Correct path (rs_decode) for messages with
+ * more than k distinct shares are rs_decode_batch's; shares that alias any
+ * message's dst are set aside first, each with its own length.
+ * The GPU pass: the messages go in staging groups -- consecutive messages
+ * while their staging (a slot of round_up(S_b, 64) bytes per shard) fits the
+ * pinned-staging cap (512 MiB; RSMI_BATCH_STAGE_MB) -- and a group is one
+ * pass of the per-job-length combine kernel (rs_combine_lens, rs_kernel_name
+ * which = 9): message b is a job of k sources.  Encode's destinations are the
+ * m parity rows, every job reading one shared copy of the encode matrix's
+ * bottom rows; decode's are the message's erased DATA shards only, from the
+ * k survivors in Rebuild's slot order (rs_pattern_survivors), with the decode
+ * rows (those of rs_pattern_rows) built once per distinct erasure set of the
+ * pass; present data shards are copied on the host while the GPU works, and a
+ * message whose k survivors all lie 16-byte aligned in engine-pinned memory
+ * is read in place (RS_STAT_BATCHES_IN_PLACE counts a pass whose messages all
+ * are, RS_STAT_BATCHES_STAGED any other).  Within a group the messages go in
+ * chunks cut at message boundaries and balanced by bytes: one chunk is staged
+ * while the previous one is coded and the one before is copied out.
+ * Pass-through: when all messages that are left to code have one length the
+ * call is the equal-length call (same pass, same counters), which sends
+ * exactly one message down the single-message path; a group of one message
+ * -- one whose own staging exceeds the cap included -- takes that path too.
+ * Device sets: contiguous message ranges, one per member, balanced by bytes.
+ * status[b] gets each message's code; both return RS_OK if every message was
+ * coded, else the first failing status in message order.  RS_EINVAL for a
+ * NULL ctx (before any HIP call), batch < 0, or a NULL array with batch > 0. */
+int rs_encode_batch_lens(rs_ctx *ctx, int batch, const uint8_t *const *inputs, const size_t *lens,
+                         uint8_t *const *parities, int *status);
+int rs_decode_batch_lens(rs_ctx *ctx, int batch, const int *counts, int *numbers, const uint8_t **shares,
+                         const size_t *share_lens, uint8_t **dsts, int *status);
 
 /* ---- device-resident batched API (many stripes per launch) ---------------
  * Stripe s, shard i lives at
@@ -489,6 +534,39 @@ typedef struct rs_combine_job {
 } rs_combine_job;
 int rs_combine(rs_ctx *ctx, const rs_combine_job *jobs, size_t count, size_t len, void *stream);
 
+/* rs_combine_lens: rs_combine with a length per job -- `len` replaced by
+ * lens[b] for job b, word for word.  lens: HOST array of `count` lengths, not
+ * retained.  round_up(lens[b], 16) bytes of each of job b's sources are read
+ * and of each of its destinations are written, and nothing past that; a store
+ * that holds objects of different sizes codes them in one call where
+ * rs_combine takes one call per distinct length.
+ * A job with lens[b] == 0 is validated like any other (NULL arrays, nsrc and
+ * nout ranges, reserved, addresses) but reads nothing, writes nothing, has no
+ * ranges for the overlap rule and is not counted in RS_STAT_COMBINE_JOBS /
+ * _ROWS.
+ * Overlap rule: rs_combine's, each range as long as its own job's span: with
+ * span_b = round_up(lens[b], 16), a dst range [d, d + span_b) of job b may
+ * meet neither a src range [s, s + span_b') of any job b' nor another dst
+ * range of the call.
+ * Bytes moved: the row groups of MG rows are chosen once for the call, from
+ * the largest nsrc and nout of the jobs that have bytes, as rs_combine does;
+ * with G_b = ceil(nout_b / MG) job b moves
+ *     (G_b * nsrc_b + nout_b * (1 + accumulate_b)) * lens[b]
+ * bytes.
+ * Kernel: jobs of different lengths run the per-job-length twin of the
+ * combine kernel (rs_kernel_name which = 9), whose blocks find their job by a
+ * search of a prefix sum of the jobs' block counts; the device tables grow
+ * with the jobs, not with the bytes.  A call whose jobs all have one length is
+ * rs_combine itself: same kernel (which = 6), same stats.
+ * All or nothing: rs_combine's refusals, and RS_EINVAL for lens == NULL with
+ * count > 0, any lens[b] of 2^28 or more 16-byte columns, or more than
+ * 2^31 - 1 blocks in all.  count == 0 or every length 0: RS_OK, nothing
+ * launched.
+ * Device sets: the call runs on the member on the device that holds the first
+ * destination of the first job with a non-zero length.
+ * Enqueued on stream; returns when queued, as rs_combine. */
+int rs_combine_lens(rs_ctx *ctx, const rs_combine_job *jobs, size_t count, const size_t *lens, void *stream);
+
 /* rs_reconstruct_ptrs: rs_reconstruct_stripes with shards anywhere in
  * device memory.  shard_ptrs is a DEVICE array [stripes][n] of device
  * addresses (16-byte aligned): shard i of stripe s is read (survivor) or
@@ -535,6 +613,8 @@ enum {
     RS_STAT_UPDATE_ABSORBED = 21,  /* erased changed shards rs_update_degraded took into the parity only */
     RS_STAT_COLUMN_STRIPES = 22,   /* inconsistent stripes rs_correct_columns handed to the column kernel */
     RS_STAT_COLUMN_BYTES = 23,     /* bytes rs_correct_columns corrected                */
+    RS_STAT_BATCH_LENS_PASSES = 24, /* GPU passes of rs_encode_batch_lens / rs_decode_batch_lens (one per staging group) */
+    RS_STAT_COMBINE_LENS_LAUNCHES = 25, /* rs_combine_lens calls served by the per-job-length kernel (not by rs_combine's) */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/rsmi.h"
+#include "combine_lens_map.hpp"
 
 namespace rsmi {
 
@@ -31,6 +32,14 @@ struct CombinePlan {
     uint32_t max_nsrc = 0;         // the largest nsrc of any job
     uint32_t max_nout = 0;         // the largest nout of any job
     uint64_t rows = 0;             // output rows of all jobs
+    // plan_combine_lens only (combine_lens_map.hpp); empty after plan_combine.
+    std::vector<uint32_t> ncols;        // 16-byte columns of each job
+    std::vector<uint32_t> first_block;  // jobs + 1 entries: exclusive prefix sum of the jobs' block counts
+    uint32_t mg = 0, groups = 0;        // combine_row_group(max_nsrc, max_nout) and the row groups of the widest job
+    uint32_t iters = 0;                 // iterations per block the block counts were made for
+    uint32_t ncols_all = 0;             // the common column count of the jobs that have columns, 0 when they differ
+    uint32_t live = 0;                  // jobs that have columns
+    uint32_t first_live = 0;            // the first of them
 };
 
 // Plans `count` jobs over buffers of `len` bytes.  RS_OK and the plan (empty
@@ -44,5 +53,18 @@ struct CombinePlan {
 // The jobs are checked in order; overlaps are looked for last, by sorting the
 // destinations (never pair by pair).
 int plan_combine(const rs_combine_job* jobs, size_t count, size_t len, CombinePlan* plan);
+
+// plan_combine with job b over buffers of lens[b] bytes: span_b =
+// round_up(lens[b], 16) in the overlap rule -- a dst range [d, d + span_b) may
+// meet neither [s, s + span_b') of a src of any job b' nor another dst range
+// -- and the block map of the per-job-length kernel (ncols, first_block, for
+// blocks of up to `iters` iterations and the call-wide row groups).  A job
+// with lens[b] == 0 is validated like any other and keeps its place in the
+// tables, but contributes no ranges to the overlap check, no blocks (a
+// repeated prefix value) and nothing to max_nsrc, max_nout and rows.
+// RS_EINVAL additionally for lens == NULL with count > 0, any lens[b] of 2^28
+// or more columns, or more than 2^31 - 1 blocks in all.  count == 0 or all
+// lengths 0: RS_OK and an empty plan.
+int plan_combine_lens(const rs_combine_job* jobs, size_t count, const size_t* lens, CombinePlan* plan, uint32_t iters = 1);
 
 }  // namespace rsmi

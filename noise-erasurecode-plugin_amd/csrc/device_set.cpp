@@ -243,4 +243,56 @@ int set_decode_batch(DeviceSet* s, int batch, const int* counts, int* numbers, c
     return RS_OK;
 }
 
+namespace {
+// Contiguous message ranges, one per member, balanced by bytes: member i's
+// range ends with the first message at which the running sum reaches
+// (i + 1) / cnt of the total (a greedy prefix split).  Returns cnt + 1 bounds.
+std::vector<size_t> split_by_bytes(const size_t* bytes, int batch, int cnt) {
+    size_t total = 0;
+    for (int b = 0; b < batch; ++b) total += bytes[b];
+    std::vector<size_t> cut(static_cast<size_t>(cnt) + 1, static_cast<size_t>(batch));
+    cut[0] = 0;
+    size_t b = 0, sum = 0;
+    for (int i = 0; i + 1 < cnt; ++i) {
+        const size_t want = total / static_cast<size_t>(cnt) * static_cast<size_t>(i + 1);
+        while (b < static_cast<size_t>(batch) && sum < want) sum += bytes[b++];
+        cut[static_cast<size_t>(i) + 1] = b;
+    }
+    return cut;
+}
+}  // namespace
+
+int set_encode_batch_lens(DeviceSet* s, int batch, const uint8_t* const* inputs, const size_t* lens, uint8_t* const* parities,
+                          int* status) {
+    const int cnt = set_count(s);
+    const std::vector<size_t> cut = split_by_bytes(lens, batch, cnt);
+    (void)set_run(s, [&](int i) -> int {
+        const size_t b0 = cut[static_cast<size_t>(i)], nb = cut[static_cast<size_t>(i) + 1] - b0;
+        if (!nb) return RS_OK;
+        return rs_encode_batch_lens(s->members[static_cast<size_t>(i)], static_cast<int>(nb), inputs + b0, lens + b0,
+                                    parities + b0, status + b0);
+    });
+    for (int b = 0; b < batch; ++b)  // the first failing status in message order
+        if (status[b] != RS_OK) return status[b];
+    return RS_OK;
+}
+
+int set_decode_batch_lens(DeviceSet* s, int batch, const int* counts, int* numbers, const uint8_t** shares,
+                          const size_t* share_lens, uint8_t** dsts, int* status) {
+    const int cnt = set_count(s);
+    const std::vector<size_t> cut = split_by_bytes(share_lens, batch, cnt);
+    // Offsets of each message's shares in numbers[] / shares[].
+    std::vector<size_t> first(static_cast<size_t>(batch) + 1, 0);
+    for (int b = 0; b < batch; ++b) first[b + 1] = first[b] + static_cast<size_t>(std::max(counts[b], 0));
+    (void)set_run(s, [&](int i) -> int {
+        const size_t b0 = cut[static_cast<size_t>(i)], nb = cut[static_cast<size_t>(i) + 1] - b0;
+        if (!nb) return RS_OK;
+        return rs_decode_batch_lens(s->members[static_cast<size_t>(i)], static_cast<int>(nb), counts + b0,
+                                    numbers + first[b0], shares + first[b0], share_lens + b0, dsts + b0, status + b0);
+    });
+    for (int b = 0; b < batch; ++b)
+        if (status[b] != RS_OK) return status[b];
+    return RS_OK;
+}
+
 }  // namespace rsmi

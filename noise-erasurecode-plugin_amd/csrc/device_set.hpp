@@ -55,5 +55,11 @@ int set_encode_batch(DeviceSet* s, int batch, const uint8_t* const* inputs, size
                      int* status);
 int set_decode_batch(DeviceSet* s, int batch, const int* counts, int* numbers, const uint8_t** shares, size_t S,
                      uint8_t** dsts, int* status);
+// The same with a length per message (rs_encode_batch_lens,
+// rs_decode_batch_lens): the ranges are balanced by bytes, not by messages.
+int set_encode_batch_lens(DeviceSet* s, int batch, const uint8_t* const* inputs, const size_t* lens, uint8_t* const* parities,
+                          int* status);
+int set_decode_batch_lens(DeviceSet* s, int batch, const int* counts, int* numbers, const uint8_t** shares,
+                          const size_t* share_lens, uint8_t** dsts, int* status);
 
 }  // namespace rsmi

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace rsmi {
 namespace {
@@ -595,8 +596,16 @@ __global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
 // came from (as the update's parity); in overwrite mode they start at zero
 // and the destinations are never read.
 // LDS: [nsrc][MG/4][20] table dwords | nsrc source pointers.
-template <int MG, int BT, bool NT>
-__global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
+//
+// VARLEN (rs_combine_lens, CombLensArgs): every job has its own column count.
+// The block finds its job by a search of first_block[] that only blockIdx
+// feeds (combine_lens_map.hpp: scalar loads, uniform across the block), in
+// natural block order, and takes every column bound -- the last column, the
+// tail-lane clamp, the end of the iterations, the chunk stride -- from that
+// job; a block never leaves its job.  a.iters is the most iterations any
+// block runs.  The equal-length instances take none of this.
+template <int MG, int BT, bool NT, bool VARLEN = false>
+__global__ __launch_bounds__(BT) void rs_combine_kernel(std::conditional_t<VARLEN, CombLensArgs, CombArgs> a) {
     extern __shared__ uint4 lds4[];
     static_assert(MG % 4 == 0, "whole sub-steps");
     constexpr int TG = MG / kRowsPerStep;  // sub-steps per source
@@ -606,11 +615,25 @@ __global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
     // where the update kernel runs four.
     constexpr int JB = 4;
 
-    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
-    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
-    b /= a.groups;
-    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
-    const CombineJob job = a.jobs[b / a.chunks];
+    uint32_t grp, chunk, chunks, ncols;
+    CombineJob job;
+    if constexpr (VARLEN) {
+        const CombineBlock at = combine_lens_block(a.first_block, a.njobs, a.groups, blockIdx.x);
+        const uint32_t jb = __builtin_amdgcn_readfirstlane(at.job);
+        grp = __builtin_amdgcn_readfirstlane(at.grp);
+        chunk = __builtin_amdgcn_readfirstlane(at.chunk);
+        chunks = __builtin_amdgcn_readfirstlane(at.chunks);
+        ncols = __builtin_amdgcn_readfirstlane(a.ncols[jb]);
+        job = a.jobs[jb];
+    } else {
+        uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+        grp = static_cast<uint32_t>(b % a.groups);
+        b /= a.groups;
+        chunk = static_cast<uint32_t>(b % a.chunks);
+        job = a.jobs[b / a.chunks];
+        chunks = a.chunks;
+        ncols = a.ncols16;
+    }
     const int nsrc = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.nsrc));
     const int nout = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.nout));
     const bool accumulate = __builtin_amdgcn_readfirstlane(job.accumulate) != 0;
@@ -630,8 +653,8 @@ __global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
 #pragma unroll
     for (int r = 0; r < MG; ++r) dp[r] = r < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(da[r])) : nullptr;
 
-    const uint32_t last = a.ncols16 - 1;
-    const uint32_t cstride = a.chunks * BT;
+    const uint32_t last = ncols - 1;
+    const uint32_t cstride = chunks * BT;
     const uint32_t col0 = chunk * BT + threadIdx.x;
     const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
     uint32_t acc[TG][kRowsPerStep][4];
@@ -671,7 +694,7 @@ __global__ __launch_bounds__(BT) void rs_combine_kernel(CombArgs a) {
     bool preloaded = true;
     for (uint32_t it = 0; it < a.iters; ++it) {
         const uint32_t colbase = chunk * BT + it * cstride;
-        if (colbase >= a.ncols16) break;
+        if (colbase >= ncols) break;
         RS_MEM_FENCE();
         const uint32_t col = colbase + threadIdx.x;
         const bool ok = col <= last;
@@ -1516,6 +1539,17 @@ struct CombineVariant {
 const CombineVariant kCombine[] = {RS_COMBINE(4), RS_COMBINE(8), RS_COMBINE(16)};
 #undef RS_COMBINE
 
+// Their per-job-length twins (rs_combine_lens), same row groups.
+struct CombineLensVariant {
+    int MG;
+    const char* name;
+    void (*fn)(CombLensArgs);
+};
+#define RS_COMBINE_LENS(MG) {MG, "combine_lens_MG" #MG "_B256", rs_combine_kernel<MG, kBlock, true, true>}
+const CombineLensVariant kCombineLens[] = {RS_COMBINE_LENS(4), RS_COMBINE_LENS(8), RS_COMBINE_LENS(16)};
+#undef RS_COMBINE_LENS
+static_assert(kCombineBlockCols == kBlock, "the block map's columns per block are the kernel's lanes");
+
 size_t combine_lds(int mg, uint32_t max_nsrc) {
     return static_cast<size_t>(max_nsrc) * (mg / kRowsPerStep) * kStepWords * 4 + static_cast<size_t>(max_nsrc) * sizeof(void*);
 }
@@ -1708,6 +1742,47 @@ hipError_t launch_combine(const CombArgs& a, uint32_t max_nsrc, hipStream_t stre
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
+
+uint32_t combine_iters_cap() {
+    static const uint32_t cap = [] {
+        const char* e = std::getenv("RSMI_ITERS");  // tuning knob, as launch_matmul
+        const int v = e ? std::atoi(e) : 1;
+        return static_cast<uint32_t>(v > 0 ? v : 1);
+    }();
+    return cap;
+}
+
+const char* combine_lens_variant_name(int nsrc, int nout) {
+    const int mg = pick_combine(static_cast<uint32_t>(nsrc), static_cast<uint32_t>(nout)).MG;
+    for (const CombineLensVariant& u : kCombineLens)
+        if (u.MG == mg) return u.name;
+    return "";
+}
+
+bool plan_combine_lens_launch(CombLensArgs* a, const CombinePlan& plan) {
+    // The planner's row groups (combine_row_group) are pick_combine's.
+    if (plan.jobs.empty() || static_cast<int>(plan.mg) != pick_combine(plan.max_nsrc, plan.max_nout).MG) return false;
+    if (plan.first_block.size() != plan.jobs.size() + 1 || plan.ncols.size() != plan.jobs.size()) return false;
+    a->njobs = static_cast<uint32_t>(plan.jobs.size());
+    a->ncols16 = 0;
+    a->chunks = 0;
+    a->xcd = 0;  // natural block order
+    a->mg = plan.mg;
+    a->groups = plan.groups;
+    a->iters = plan.iters;
+    return true;
+}
+
+hipError_t launch_combine_lens(const CombLensArgs& a, uint32_t max_nsrc, uint32_t blocks, hipStream_t stream) {
+    if (a.njobs == 0 || blocks == 0 || max_nsrc == 0) return hipSuccess;
+    const CombineLensVariant* v = nullptr;
+    for (const CombineLensVariant& u : kCombineLens)
+        if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
+    const size_t lds = combine_lds(static_cast<int>(a.mg), max_nsrc);
+    if (!v || lds > kUpdateLdsMax || a.groups == 0 || a.iters == 0 || blocks > 0x7FFFFFFFu) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v->fn, dim3(blocks), dim3(kBlock), lds, stream, a);
     return hipGetLastError();
 }
 

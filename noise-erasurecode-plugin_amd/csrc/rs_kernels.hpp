@@ -221,6 +221,25 @@ bool plan_combine_launch(CombArgs* a, uint32_t max_nsrc, uint32_t max_nout);
 hipError_t launch_combine(const CombArgs& a, uint32_t max_nsrc, hipStream_t stream);  // a: planned
 const char* combine_variant_name(int nsrc, int nout);  // "combine_MG4_B256" etc.
 
+// rs_combine_lens: CombArgs for jobs of their own lengths.  Job b has ncols[b]
+// 16-byte columns and owns the blocks [first_block[b], first_block[b + 1]) of
+// the grid (combine_lens_map.hpp); ncols16, chunks and xcd are unused (natural
+// block order), iters is the most iterations any block runs.
+struct CombLensArgs : CombArgs {
+    const uint32_t* ncols;        // [njobs] (device)
+    const uint32_t* first_block;  // [njobs + 1] (device)
+};
+// The iterations a block of the combine kernels may run (RSMI_ITERS, 1 unless
+// set): what plan_combine_lens makes its block counts for.
+uint32_t combine_iters_cap();
+// Fills in the launch plan from a plan_combine_lens plan (njobs, groups, mg,
+// iters); false when the plan's row groups are not those of the kernel
+// variants.
+bool plan_combine_lens_launch(CombLensArgs* a, const CombinePlan& plan);
+// a: planned; blocks = the plan's first_block.back().
+hipError_t launch_combine_lens(const CombLensArgs& a, uint32_t max_nsrc, uint32_t blocks, hipStream_t stream);
+const char* combine_lens_variant_name(int nsrc, int nout);  // "combine_lens_MG4_B256" etc.
+
 // Degraded read (rs_read_stripes): job b = {stripe, first, j} of `jobs`, whose
 // stripe uses decode pattern pats[b] of the ctx's pattern cache, regenerates
 // the j wanted missing shards entries[first .. first + j) from the pattern's k

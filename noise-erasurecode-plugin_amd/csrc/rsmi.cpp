@@ -373,6 +373,8 @@ struct rs_ctx {
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
+    std::atomic<int64_t> batch_lens_passes{0};                           // GPU passes of rs_encode_batch_lens / rs_decode_batch_lens
+    std::atomic<int64_t> combine_lens_launches{0};                       // rs_combine_lens calls the per-job-length kernel served
     std::atomic<int64_t> update_degraded{0}, update_absorbed{0};         // rs_update_degraded (rs_stat)
     std::atomic<int64_t> column_stripes{0}, column_bytes{0};             // rs_correct_columns (rs_stat)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
@@ -1255,6 +1257,62 @@ int combine(rs_ctx* c, Lease& L, const rsmi::CombinePlan& plan, rsmi::CombArgs a
     if (e == hipSuccess) {
         c->combine_jobs += static_cast<int64_t>(njobs);
         c->combine_rows += static_cast<int64_t>(plan.rows);
+    }
+    return finish_launch(c, L, s, false, hip_status(e));
+}
+
+// The equal-length combine kernel over a routed call's plan: jobs of ncols16
+// 16-byte columns each.
+int combine_equal(rs_ctx* c, const rsmi::CombinePlan& plan, uint32_t ncols16, hipStream_t s) {
+    rsmi::CombArgs a{};
+    a.ncols16 = ncols16;
+    a.njobs = static_cast<uint32_t>(plan.jobs.size());
+    a.xcd = c->xcd_update;
+    if (!rsmi::plan_combine_launch(&a, plan.max_nsrc, plan.max_nout)) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return combine(c, *sc.L, plan, a, s);
+}
+
+// The tables of a per-job-length combine on stream s through lease L, in one
+// upload (upload_tables): combine()'s and, behind them, the jobs' column
+// counts and the block map (combine_lens_map.hpp; one prefix sum for
+// rs_combine_lens, one per chunk of messages for the batch calls).  Sets a's
+// table pointers.
+int upload_combine_lens(rs_ctx* c, Lease& L, const rsmi::CombinePlan& plan, hipStream_t s, rsmi::CombLensArgs* a) {
+    const size_t njobs = plan.jobs.size();
+    const size_t addr_off = njobs * sizeof(rsmi::CombineJob);
+    const size_t coef_off = addr_off + plan.addrs.size() * sizeof(uint64_t);
+    const size_t ncols_off = round_up(coef_off + plan.coef.size(), sizeof(uint32_t));
+    const size_t first_off = ncols_off + njobs * sizeof(uint32_t);
+    const size_t bytes = first_off + plan.first_block.size() * sizeof(uint32_t);
+    Tables t;
+    const int up = upload_tables(c, L, 0, bytes, s, &t, [&](uint8_t* hb) {
+        std::memcpy(hb, plan.jobs.data(), addr_off);
+        std::memcpy(hb + addr_off, plan.addrs.data(), coef_off - addr_off);
+        std::memcpy(hb + coef_off, plan.coef.data(), plan.coef.size());
+        std::memcpy(hb + ncols_off, plan.ncols.data(), first_off - ncols_off);
+        std::memcpy(hb + first_off, plan.first_block.data(), bytes - first_off);
+    });
+    if (up != RS_OK) return up;
+    a->jobs = reinterpret_cast<const rsmi::CombineJob*>(t.dev);
+    a->addrs = reinterpret_cast<const uint64_t*>(t.dev + addr_off);
+    a->coef = t.dev + coef_off;
+    a->ncols = reinterpret_cast<const uint32_t*>(t.dev + ncols_off);
+    a->first_block = reinterpret_cast<const uint32_t*>(t.dev + first_off);
+    return RS_OK;
+}
+
+// rs_combine_lens on stream s with lease L: the tables, then the
+// per-job-length twin of the combine kernel.
+int combine_lens(rs_ctx* c, Lease& L, const rsmi::CombinePlan& plan, rsmi::CombLensArgs a, hipStream_t s) {
+    const int up = upload_combine_lens(c, L, plan, s, &a);
+    if (up != RS_OK) return up;
+    const hipError_t e = rsmi::launch_combine_lens(a, plan.max_nsrc, plan.first_block.back(), s);
+    if (e == hipSuccess) {
+        c->combine_jobs += static_cast<int64_t>(plan.live);
+        c->combine_rows += static_cast<int64_t>(plan.rows);
+        ++c->combine_lens_launches;
     }
     return finish_launch(c, L, s, false, hip_status(e));
 }
@@ -3077,6 +3135,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 6) return rsmi::combine_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 7) return rsmi::update_degraded_variant_name(c->m);
     if (which == 8) return rsmi::column_variant_name(c->m);
+    if (which == 9) return rsmi::combine_lens_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3139,6 +3198,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_UPDATE_ABSORBED: return c->update_absorbed.load();
         case RS_STAT_COLUMN_STRIPES: return c->column_stripes.load();
         case RS_STAT_COLUMN_BYTES: return c->column_bytes.load();
+        case RS_STAT_BATCH_LENS_PASSES: return c->batch_lens_passes.load();
+        case RS_STAT_COMBINE_LENS_LAUNCHES: return c->combine_lens_launches.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3451,14 +3512,33 @@ int rs_combine(rs_ctx* c, const rs_combine_job* jobs, size_t count, size_t len, 
     if (rc != RS_OK) return rc;
     // A device set: the member on the device of the first destination.
     if (!route(c, reinterpret_cast<const void*>(static_cast<uintptr_t>(plan.addrs[plan.jobs[0].nsrc])))) return RS_EINVAL;
-    rsmi::CombArgs a{};
-    a.ncols16 = static_cast<uint32_t>(round_up(len, 16) / 16);
-    a.njobs = static_cast<uint32_t>(plan.jobs.size());
-    a.xcd = c->xcd_update;
-    if (!rsmi::plan_combine_launch(&a, plan.max_nsrc, plan.max_nout)) return RS_EINVAL;
+    return combine_equal(c, plan, static_cast<uint32_t>(round_up(len, 16) / 16), static_cast<hipStream_t>(stream));
+}
+
+int rs_combine_lens(rs_ctx* c, const rs_combine_job* jobs, size_t count, const size_t* lens, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0) return RS_OK;
+    rsmi::CombinePlan plan;
+    const int rc = rsmi::plan_combine_lens(jobs, count, lens, &plan, rsmi::combine_iters_cap());
+    if (rc != RS_OK) return rc;
+    if (plan.jobs.empty()) return RS_OK;  // no job has any bytes
+    // A device set: the member on the device of the first destination of the
+    // first job that has bytes.
+    const rsmi::CombineJob& first = plan.jobs[plan.first_live];
+    if (!route(c, reinterpret_cast<const void*>(static_cast<uintptr_t>(plan.addrs[first.addr + first.nsrc])))) return RS_EINVAL;
+    // One length for every job: the call is rs_combine, kernel and all.
+    // RSMI_COMBINE_LENS_FORCE=1 (measurements only) keeps it on the twin.
+    static const bool force = [] {
+        const char* e = std::getenv("RSMI_COMBINE_LENS_FORCE");
+        return e && std::atoi(e) != 0;
+    }();
+    if (!force && plan.ncols_all != 0 && plan.live == plan.jobs.size())
+        return combine_equal(c, plan, plan.ncols_all, static_cast<hipStream_t>(stream));
+    rsmi::CombLensArgs a{};
+    if (!rsmi::plan_combine_lens_launch(&a, plan)) return RS_EINVAL;
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
-    return combine(c, *sc.L, plan, a, static_cast<hipStream_t>(stream));
+    return combine_lens(c, *sc.L, plan, a, static_cast<hipStream_t>(stream));
 }
 
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
@@ -3586,6 +3666,36 @@ size_t batch_stage_cap() {
     return cap;
 }
 
+// One message of a decode batch, with rs_decode's semantics: validates its
+// `cnt` shares and sorts them by number in place (nb, sb: its slices of the
+// caller's arrays); by_id[i] = the first share numbered i.  RS_OK: exactly k
+// distinct shares (the batched pass); 1: more than k (the Correct path);
+// otherwise the message's failure.
+int sort_message(int k, int n, int cnt, int* nb, const uint8_t** sb, std::vector<const uint8_t*>& by_id) {
+    if (cnt < k) return RS_ENOT_ENOUGH;
+    for (int i = 0; i < cnt; ++i)
+        if (nb[i] < 0 || nb[i] >= n) return RS_EBAD_SHARE_ID;
+    std::vector<int> order(cnt);
+    for (int i = 0; i < cnt; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nb[x] < nb[y]; });
+    std::vector<int> nums(cnt);
+    std::vector<const uint8_t*> ptrs(cnt);
+    for (int i = 0; i < cnt; ++i) {
+        nums[i] = nb[order[i]];
+        ptrs[i] = sb[order[i]];
+    }
+    std::copy(nums.begin(), nums.end(), nb);
+    std::copy(ptrs.begin(), ptrs.end(), sb);
+    by_id.assign(n, nullptr);
+    int distinct = 0;
+    for (int i = 0; i < cnt; ++i)
+        if (!by_id[nums[i]]) {
+            by_id[nums[i]] = ptrs[i];
+            ++distinct;
+        }
+    return distinct < k ? RS_ESINGULAR : distinct > k ? 1 : static_cast<int>(RS_OK);
+}
+
 // Chunks of messages for the direct batch forms: one per 256 KiB of input
 // bytes, at most kBatchChunks (their events) and one message each at least
 // -- two config-1 messages already run as two chunks, the first coded while
@@ -3666,58 +3776,20 @@ int rs_decode_batch(rs_ctx* c, int batch, const int* counts, int* numbers, const
     for (int b = 0; b < batch; ++b) first[b + 1] = first[b] + static_cast<size_t>(std::max(counts[b], 0));
     std::vector<int> fast;  // messages for the batched launch
     std::vector<std::vector<const uint8_t*>> by(batch);
-    int rc = RS_OK;
     for (int b = 0; b < batch; ++b) {
-        int* nb = numbers + first[b];
-        const uint8_t** sb = shares + first[b];
-        const int cnt = counts[b];
-        status[b] = RS_OK;
-        if (cnt < k) status[b] = RS_ENOT_ENOUGH;
-        for (int i = 0; i < cnt && status[b] == RS_OK; ++i)
-            if (nb[i] < 0 || nb[i] >= n) status[b] = RS_EBAD_SHARE_ID;
-        if (status[b] != RS_OK) {
-            if (rc == RS_OK) rc = status[b];
-            continue;
-        }
-        std::vector<int> order(cnt);
-        for (int i = 0; i < cnt; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return nb[x] < nb[y]; });
-        std::vector<int> nums(cnt);
-        std::vector<const uint8_t*> ptrs(cnt);
-        for (int i = 0; i < cnt; ++i) {
-            nums[i] = nb[order[i]];
-            ptrs[i] = sb[order[i]];
-        }
-        std::copy(nums.begin(), nums.end(), nb);
-        std::copy(ptrs.begin(), ptrs.end(), sb);
-        by[b].assign(n, nullptr);
-        int distinct = 0;
-        for (int i = 0; i < cnt; ++i)
-            if (!by[b][nums[i]]) {
-                by[b][nums[i]] = ptrs[i];
-                ++distinct;
-            }
-        if (distinct < k) {
-            status[b] = RS_ESINGULAR;
-            if (rc == RS_OK) rc = status[b];
-        } else if (distinct > k) {
-            status[b] = 1;  // Correct path, below
-        } else if (S > 0) {
-            fast.push_back(b);
-        }
+        status[b] = sort_message(k, n, counts[b], numbers + first[b], shares + first[b], by[b]);
+        if (status[b] == RS_OK && S > 0) fast.push_back(b);
     }
     // 2. messages needing Correct: one by one
     for (int b = 0; b < batch; ++b) {
         if (status[b] != 1) continue;
         status[b] = rs_decode(c, numbers + first[b], shares + first[b], counts[b], S, dsts[b]);
-        if (status[b] != RS_OK && rc == RS_OK) rc = status[b];
     }
     auto first_fail = [&] {  // the call's result: the first failing status in message order
         for (int b = 0; b < batch; ++b)
             if (status[b] != RS_OK) return status[b];
         return static_cast<int>(RS_OK);
     };
-    (void)rc;
     if (fast.empty()) return first_fail();
     if (fast.size() == 1) {  // one message: the single-message path (two staged column chunks)
         const int b = fast[0];
@@ -4083,6 +4155,409 @@ int rs_encode_batch(rs_ctx* c, int batch, const uint8_t* const* inputs, size_t l
     for (int b = 0; b < batch; ++b)  // the first failing status in message order
         if (status[b] != RS_OK) return status[b];
     return RS_OK;
+}
+
+namespace {
+// One message of a GPU pass of the mixed-length batch calls: `out.size()`
+// rows, each the combination of the k sources by one row of its coefficients.
+struct LensMsg {
+    size_t S = 0;                     // bytes per shard
+    std::vector<const uint8_t*> src;  // the k sources (host), in slot order
+    std::vector<uint64_t> src_dev;    // their device addresses when they are read in place; empty: staged
+    std::vector<uint8_t*> out;        // where the coded rows go (host)
+    uint32_t coef = 0;                // byte offset of its out.size() x k coefficients in the pass's table
+};
+
+// One GPU pass of rs_encode_batch_lens / rs_decode_batch_lens over `msgs`
+// (each with rows to code): every shard gets a staging slot of round_up(S, 64)
+// bytes in the lease's pinned batch buffer -- the sources that are not read in
+// place, then the coded rows -- and message j is job j of the per-job-length
+// combine kernel, which reads and writes the staging over PCIe.  The messages
+// go in chunks cut at message boundaries and balanced by bytes: chunk i + 1 is
+// staged while chunk i is coded and chunk i - 1 is copied out.  No overlap
+// validation: the engine owns the addresses.  while_gpu (optional) runs once
+// every chunk is launched.
+int lens_pass(rs_ctx* c, Lease& L, const std::vector<LensMsg>& msgs, const std::vector<uint8_t>& coef,
+              const std::function<void()>& while_gpu) {
+    const size_t B = msgs.size(), k = static_cast<size_t>(c->k);
+    rsmi::HostPipeline* pipe = L.pipeline();
+    if (!pipe) return RS_ENOMEM;
+    const hipStream_t s = L.stream;
+    size_t in_bytes = 0, out_bytes = 0, moved = 0;
+    rsmi::CombinePlan plan;
+    for (const LensMsg& m : msgs) {
+        const size_t sp = round_up(m.S, 64);
+        if (m.src_dev.empty()) in_bytes += k * sp;
+        out_bytes += m.out.size() * sp;
+        moved += k * sp;
+        plan.max_nout = std::max<uint32_t>(plan.max_nout, static_cast<uint32_t>(m.out.size()));
+        plan.rows += m.out.size();
+    }
+    if (!L.st_batch.acquire(in_bytes + out_bytes)) return RS_ENOMEM;
+    uint8_t* h = static_cast<uint8_t*>(L.st_batch.p);
+    const uint64_t hd = reinterpret_cast<uint64_t>(L.st_batch.dev);
+    // The plan, built in place of plan_combine_lens.
+    plan.max_nsrc = static_cast<uint32_t>(k);
+    plan.mg = rsmi::combine_row_group(plan.max_nsrc, plan.max_nout);
+    plan.groups = (plan.max_nout + plan.mg - 1) / plan.mg;
+    plan.iters = rsmi::combine_iters_cap();
+    plan.coef = coef;
+    plan.live = static_cast<uint32_t>(B);
+    std::vector<size_t> in_off(B), out_off(B);
+    size_t in_at = 0, out_at = in_bytes;
+    for (size_t j = 0; j < B; ++j) {
+        const LensMsg& m = msgs[j];
+        const size_t sp = round_up(m.S, 64);
+        plan.jobs.push_back(rsmi::CombineJob{static_cast<uint32_t>(plan.addrs.size()), m.coef, static_cast<uint16_t>(k),
+                                             static_cast<uint16_t>(m.out.size()), 0});
+        in_off[j] = in_at;
+        out_off[j] = out_at;
+        for (size_t i = 0; i < k; ++i) plan.addrs.push_back(m.src_dev.empty() ? hd + in_at + i * sp : m.src_dev[i]);
+        if (m.src_dev.empty()) in_at += k * sp;
+        for (size_t t = 0; t < m.out.size(); ++t) plan.addrs.push_back(hd + out_at + t * sp);
+        out_at += m.out.size() * sp;
+        plan.ncols.push_back(static_cast<uint32_t>(round_up(m.S, 16) / 16));
+    }
+    // Chunk ch = messages [cut[ch], cut[ch + 1]), with a block map of its own.
+    const size_t nch = direct_batch_chunks(B, moved);
+    std::vector<size_t> cut(nch + 1, B);
+    cut[0] = 0;
+    {
+        size_t j = 0, bytes = 0;
+        for (size_t ch = 0; ch + 1 < nch; ++ch) {
+            const size_t want = moved / nch * (ch + 1);
+            do bytes += k * round_up(msgs[j++].S, 64);
+            while (bytes < want && j < B - (nch - 1 - ch));
+            cut[ch + 1] = j;
+        }
+    }
+    for (size_t ch = 0; ch < nch; ++ch) {
+        uint64_t blocks = 0;
+        for (size_t j = cut[ch]; j < cut[ch + 1]; ++j) {
+            plan.first_block.push_back(static_cast<uint32_t>(blocks));
+            blocks += static_cast<uint64_t>(rsmi::combine_lens_chunks(plan.ncols[j], plan.iters)) * plan.groups;
+        }
+        if (blocks > 0x7FFFFFFFull) return RS_EINVAL;
+        plan.first_block.push_back(static_cast<uint32_t>(blocks));
+    }
+    rsmi::CombLensArgs a{};
+    a.mg = plan.mg;
+    a.groups = plan.groups;
+    a.iters = plan.iters;
+    const int up = upload_combine_lens(c, L, plan, s, &a);  // orders s after the lease's previous device use
+    if (up != RS_OK) return up;
+    const rsmi::CombLensArgs base = a;
+    hipError_t e = hipSuccess;
+    size_t launched = 0;
+    for (size_t ch = 0; ch < nch && e == hipSuccess; ++ch) {
+        const size_t j0 = cut[ch], j1 = cut[ch + 1];
+        std::vector<rsmi::CopyPool::Piece> in;
+        for (size_t j = j0; j < j1; ++j) {
+            if (!msgs[j].src_dev.empty()) continue;
+            const size_t sp = round_up(msgs[j].S, 64);
+            for (size_t i = 0; i < k; ++i) in.push_back({h + in_off[j] + i * sp, msgs[j].src[i], msgs[j].S, true});
+        }
+        pipe->copy(in);
+        a = base;
+        a.jobs = base.jobs + j0;
+        a.ncols = base.ncols + j0;
+        a.first_block = base.first_block + j0 + ch;
+        a.njobs = static_cast<uint32_t>(j1 - j0);
+        e = rsmi::launch_combine_lens(a, plan.max_nsrc, plan.first_block[j1 + ch], s);
+        if (e == hipSuccess) e = hipEventRecord(L.ev[ch], s);
+        if (e == hipSuccess) ++launched;
+    }
+    L.end(s);
+    if (e == hipSuccess && while_gpu) while_gpu();
+    for (size_t ch = 0; ch < launched && e == hipSuccess; ++ch) {
+        e = rsmi::wait_event(L.ev[ch]);
+        if (e != hipSuccess) break;
+        std::vector<rsmi::CopyPool::Piece> out;
+        for (size_t j = cut[ch]; j < cut[ch + 1]; ++j) {
+            const size_t sp = round_up(msgs[j].S, 64);
+            for (size_t t = 0; t < msgs[j].out.size(); ++t) out.push_back({msgs[j].out[t], h + out_off[j] + t * sp, msgs[j].S});
+        }
+        pipe->copy(out);
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);  // nothing may still read the staging
+        return RS_EDEVICE;
+    }
+    ++c->batch_lens_passes;
+    return RS_OK;
+}
+
+// Consecutive staging groups of the messages `need` (staging bytes each): a
+// group grows while its sum fits batch_stage_cap(); a message whose own
+// staging exceeds the cap, or whose shards the kernels' 32-bit column offsets
+// do not reach (alone[j]), is a group by itself.  ends: the groups' ends.
+void lens_groups(const std::vector<size_t>& need, const std::vector<uint8_t>& alone, std::vector<size_t>& ends) {
+    for (size_t g0 = 0; g0 < need.size();) {
+        size_t g1 = g0, bytes = 0;
+        while (g1 < need.size()) {
+            const bool single = alone[g1] || need[g1] > batch_stage_cap();
+            if (g1 > g0 && (single || bytes + need[g1] > batch_stage_cap())) break;
+            bytes += need[g1++];
+            if (single) break;
+        }
+        ends.push_back(g1);
+        g0 = g1;
+    }
+}
+}  // namespace
+
+int rs_encode_batch_lens(rs_ctx* c, int batch, const uint8_t* const* inputs, const size_t* lens, uint8_t* const* parities,
+                         int* status) {
+    if (!c || batch < 0 || (batch && (!inputs || !lens || !parities || !status))) return RS_EINVAL;
+    rsmi::trace_begin();
+    struct TraceEnd {
+        ~TraceEnd() { rsmi::trace_end(); }
+    } trace_end_at_exit;
+    if (c->set) return rsmi::set_encode_batch_lens(c->set, batch, inputs, lens, parities, status);
+    const size_t k = static_cast<size_t>(c->k), m = static_cast<size_t>(c->m);
+    std::vector<int> todo;
+    for (int b = 0; b < batch; ++b) {
+        status[b] = RS_OK;
+        if (lens[b] % k != 0) status[b] = RS_ELEN_NOT_MULTIPLE;
+        else if (lens[b] == 0 || m == 0) continue;
+        else if (!inputs[b] || !parities[b]) status[b] = RS_EINVAL;
+        else todo.push_back(b);
+    }
+    auto first_fail = [&] {  // the call's result: the first failing status in message order
+        for (int b = 0; b < batch; ++b)
+            if (status[b] != RS_OK) return status[b];
+        return static_cast<int>(RS_OK);
+    };
+    if (todo.empty()) return first_fail();
+    bool one_len = true;
+    for (int b : todo) one_len &= lens[b] == lens[todo[0]];
+    if (one_len) {
+        // One length (or one message): the equal-length call, pass and counters.
+        std::vector<const uint8_t*> in;
+        std::vector<uint8_t*> par;
+        for (int b : todo) in.push_back(inputs[b]), par.push_back(parities[b]);
+        std::vector<int> st(todo.size(), RS_OK);
+        (void)rs_encode_batch(c, static_cast<int>(todo.size()), in.data(), lens[todo[0]], par.data(), st.data());
+        for (size_t j = 0; j < todo.size(); ++j) status[todo[j]] = st[j];
+        return first_fail();
+    }
+    std::vector<size_t> need(todo.size());
+    std::vector<uint8_t> alone(todo.size(), 0);
+    for (size_t j = 0; j < todo.size(); ++j) {
+        const size_t S = lens[todo[j]] / k;
+        need[j] = (k + m) * round_up(S, 64);
+        alone[j] = round_up(S, 16) / 16 >= (size_t(1) << 28);
+    }
+    const std::vector<uint8_t> bottom(c->enc.begin() + static_cast<ptrdiff_t>(k * k), c->enc.end());  // one copy serves every job
+    std::vector<size_t> ends;
+    lens_groups(need, alone, ends);
+    size_t g0 = 0;
+    for (size_t g1 : ends) {
+        if (g1 - g0 == 1) {  // one message: the single-message path
+            const int b = todo[g0];
+            status[b] = rs_encode(c, inputs[b], lens[b], parities[b]);
+        } else {
+            std::vector<LensMsg> msgs(g1 - g0);
+            for (size_t j = g0; j < g1; ++j) {
+                const int b = todo[j];
+                LensMsg& msg = msgs[j - g0];
+                msg.S = lens[b] / k;
+                for (size_t i = 0; i < k; ++i) msg.src.push_back(inputs[b] + i * msg.S);
+                for (size_t t = 0; t < m; ++t) msg.out.push_back(parities[b] + t * msg.S);
+            }
+            int rc = RS_OK;
+            {
+                DeviceGuard g(c->device);
+                LeaseGuard lg(c);
+                rc = !g.ok ? RS_EDEVICE : !lg.L ? RS_ENOMEM : lens_pass(c, *lg.L, msgs, bottom, nullptr);
+            }
+            if (rc != RS_OK) {  // a message not coded gets the call's failure (never a stale RS_OK)
+                for (size_t j = g0; j < todo.size(); ++j) status[todo[j]] = rc;
+                break;
+            }
+        }
+        g0 = g1;
+    }
+    return first_fail();
+}
+
+int rs_decode_batch_lens(rs_ctx* c, int batch, const int* counts, int* numbers, const uint8_t** shares,
+                         const size_t* share_lens, uint8_t** dsts, int* status) {
+    if (!c || batch < 0 || (batch && (!counts || !numbers || !shares || !share_lens || !dsts || !status)))
+        return RS_EINVAL;
+    if (batch == 0) return RS_OK;
+    {
+        bool one_len = true;
+        for (int b = 1; b < batch; ++b) one_len &= share_lens[b] == share_lens[0];
+        if (one_len) return rs_decode_batch(c, batch, counts, numbers, shares, share_lens[0], dsts, status);
+    }
+    rsmi::trace_begin();
+    struct TraceEnd {
+        ~TraceEnd() { rsmi::trace_end(); }
+    } trace_end_at_exit;
+    const int k = c->k, n = c->n;
+    std::vector<size_t> first(batch + 1, 0);
+    for (int b = 0; b < batch; ++b) first[b + 1] = first[b] + static_cast<size_t>(std::max(counts[b], 0));
+    {
+        // Shares that alias any message's dst are set aside first, each with
+        // its message's length (rs_decode_batch), and the call runs on a
+        // pointer array that names the copies; the caller's array is sorted
+        // like it.
+        OutRanges out;
+        for (int b = 0; b < batch; ++b) out.add(dsts[b], static_cast<size_t>(k) * share_lens[b]);
+        out.seal();
+        size_t bytes = 0;
+        for (int b = 0; b < batch; ++b)
+            for (size_t j = first[b]; j < first[b + 1]; ++j)
+                if (shares[j] && out.meets(shares[j], share_lens[b])) bytes += share_lens[b];
+        if (bytes) {
+            std::vector<uint8_t> aside(bytes);
+            std::vector<const uint8_t*> loc(shares, shares + first[batch]);
+            std::vector<std::pair<const uint8_t*, const uint8_t*>> moved;  // {copy, the caller's pointer}, by copy address
+            size_t at = 0;
+            for (int b = 0; b < batch; ++b)
+                for (size_t j = first[b]; j < first[b + 1]; ++j)
+                    if (shares[j] && out.meets(shares[j], share_lens[b])) {
+                        std::memcpy(aside.data() + at, shares[j], share_lens[b]);
+                        loc[j] = aside.data() + at;
+                        moved.push_back({loc[j], shares[j]});
+                        at += share_lens[b];
+                    }
+            const int rc = rs_decode_batch_lens(c, batch, counts, numbers, loc.data(), share_lens, dsts, status);
+            for (size_t j = 0; j < first[batch]; ++j) {
+                const auto it = std::lower_bound(moved.begin(), moved.end(), std::make_pair(loc[j], static_cast<const uint8_t*>(nullptr)));
+                shares[j] = (it != moved.end() && it->first == loc[j]) ? it->second : loc[j];
+            }
+            return rc;
+        }
+    }
+    if (c->set) return rsmi::set_decode_batch_lens(c->set, batch, counts, numbers, shares, share_lens, dsts, status);
+    // 1. validate + sort each message (rs_decode semantics); 2. the Correct
+    //    path for those with more than k distinct shares, one by one.
+    std::vector<int> fast;  // messages for the batched passes
+    std::vector<std::vector<const uint8_t*>> by(batch);
+    for (int b = 0; b < batch; ++b) {
+        status[b] = sort_message(k, n, counts[b], numbers + first[b], shares + first[b], by[b]);
+        if (status[b] == RS_OK && share_lens[b] > 0) fast.push_back(b);
+    }
+    auto decode_alone = [&](int b) {
+        status[b] = rs_decode(c, numbers + first[b], shares + first[b], counts[b], share_lens[b], dsts[b]);
+    };
+    for (int b = 0; b < batch; ++b)
+        if (status[b] == 1) decode_alone(b);
+    auto first_fail = [&] {  // the call's result: the first failing status in message order
+        for (int b = 0; b < batch; ++b)
+            if (status[b] != RS_OK) return status[b];
+        return static_cast<int>(RS_OK);
+    };
+    if (fast.empty()) return first_fail();
+    bool one_len = true;
+    for (int b : fast) one_len &= share_lens[b] == share_lens[fast[0]];
+    if (one_len) {
+        // One length (or one message) left to code: the equal-length call on
+        // those messages, pass and counters.  They are sorted already.
+        std::vector<int> cnt, nums, st(fast.size(), RS_OK);
+        std::vector<const uint8_t*> sh;
+        std::vector<uint8_t*> ds;
+        for (int b : fast) {
+            cnt.push_back(counts[b]);
+            nums.insert(nums.end(), numbers + first[b], numbers + first[b + 1]);
+            sh.insert(sh.end(), shares + first[b], shares + first[b + 1]);
+            ds.push_back(dsts[b]);
+        }
+        (void)rs_decode_batch(c, static_cast<int>(fast.size()), cnt.data(), nums.data(), sh.data(), share_lens[fast[0]],
+                              ds.data(), st.data());
+        for (size_t j = 0; j < fast.size(); ++j) status[fast[j]] = st[j];
+        return first_fail();
+    }
+    // 3. the rest, in staging groups (k survivors and at most k regenerated
+    //    rows each): a group of one message takes the single-message path, any
+    //    other one pass of the per-job-length combine kernel.
+    std::vector<size_t> need(fast.size());
+    std::vector<uint8_t> alone(fast.size(), 0);
+    for (size_t j = 0; j < fast.size(); ++j) {
+        const size_t S = share_lens[fast[j]];
+        need[j] = 2 * static_cast<size_t>(k) * round_up(S, 64);
+        alone[j] = round_up(S, 16) / 16 >= (size_t(1) << 28);
+    }
+    const bool direct_ok = std::getenv("RSMI_NO_DIRECT") == nullptr;
+    std::vector<size_t> ends;
+    lens_groups(need, alone, ends);
+    size_t g0 = 0;
+    for (size_t g1 : ends) {
+        if (g1 - g0 == 1) {
+            decode_alone(fast[g0]);
+            g0 = g1;
+            continue;
+        }
+        // Job j: the k survivors of message j in Rebuild's slot order, into its
+        // erased data shards only (erased parity is not returned); the decode
+        // rows once per distinct erasure set of the pass.
+        std::vector<LensMsg> msgs;
+        std::vector<int> msg_of;  // msgs[j] is message msg_of[j]
+        std::vector<uint8_t> coef;
+        std::map<std::vector<uint8_t>, uint32_t> coef_of;
+        std::vector<rsmi::CopyPool::Piece> direct;  // present data shards: no GPU
+        bool all_in_place = true;
+        for (size_t j = g0; j < g1; ++j) {
+            const int b = fast[j];
+            const size_t S = share_lens[b];
+            std::vector<uint8_t> present(n, 0);
+            for (int i = 0; i < n; ++i) present[i] = by[b][i] != nullptr;
+            std::vector<int> missing;
+            for (int i = 0; i < k; ++i) {
+                uint8_t* d = dsts[b] + static_cast<size_t>(i) * S;
+                if (!present[i]) missing.push_back(i);
+                else if (d != by[b][i]) direct.push_back({d, by[b][i], S});
+            }
+            if (missing.empty()) continue;
+            const std::vector<int> surv = rsmi::choose_survivors(present.data(), k, n);
+            auto known = coef_of.find(present);
+            if (known == coef_of.end()) {
+                std::vector<uint8_t> rows;
+                if (!rsmi::decode_rows(c->enc, k, n, surv, missing, rows)) {
+                    status[b] = RS_ESINGULAR;
+                    continue;
+                }
+                known = coef_of.emplace(present, static_cast<uint32_t>(coef.size())).first;
+                coef.insert(coef.end(), rows.begin(), rows.end());
+            }
+            LensMsg msg;
+            msg.S = S;
+            msg.coef = known->second;
+            bool in_place = direct_ok;
+            for (int i = 0; i < k; ++i) {
+                const uint8_t* p = by[b][surv[i]];
+                msg.src.push_back(p);
+                const uint64_t d = (!in_place || (reinterpret_cast<uintptr_t>(p) & 15u)) ? 0 : rsmi::pinned_device_address(p, round_up(S, 16));
+                in_place = d != 0;
+                msg.src_dev.push_back(d);
+            }
+            if (!in_place) msg.src_dev.clear();
+            all_in_place &= in_place;
+            for (int i : missing) msg.out.push_back(dsts[b] + static_cast<size_t>(i) * S);
+            msgs.push_back(std::move(msg));
+            msg_of.push_back(b);
+        }
+        int rc = RS_OK;
+        if (msgs.empty()) {
+            rsmi::CopyPool::shared().run(direct);
+        } else {
+            ++(all_in_place ? c->batches_in_place : c->batches_staged);
+            DeviceGuard g(c->device);
+            LeaseGuard lg(c);
+            rc = !g.ok ? RS_EDEVICE
+                 : !lg.L ? RS_ENOMEM
+                         : lens_pass(c, *lg.L, msgs, coef, [&] { rsmi::CopyPool::shared().run(direct); });
+        }
+        // A failure of the pass fails every message it carried (their outputs
+        // were not all produced).
+        if (rc != RS_OK)
+            for (size_t j = g0; j < g1; ++j)
+                if (status[fast[j]] == RS_OK) status[fast[j]] = rc;
+        g0 = g1;
+    }
+    return first_fail();
 }
 
 int rs_blake2b_device(rs_ctx* c, int count, const uint64_t* msg_ptrs, const uint64_t* lens, const uint32_t* order,

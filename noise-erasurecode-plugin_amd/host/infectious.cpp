@@ -81,6 +81,28 @@ Status FEC::EncodeBatch(const std::vector<const uint8_t*>& inputs, size_t len,
     return rc == RS_OK ? Status::Ok() : from(rc, "EncodeBatch");
 }
 
+Status FEC::EncodeBatchLens(const std::vector<const uint8_t*>& inputs, const std::vector<size_t>& lens,
+                            std::vector<std::vector<uint8_t>>* parity, std::vector<Status>* st) {
+    const int B = static_cast<int>(inputs.size());
+    parity->assign(B, {});
+    st->assign(B, Status::Ok());
+    if (lens.size() != inputs.size()) return from(RS_EINVAL, "EncodeBatchLens");
+    if (B == 0) return Status::Ok();
+    std::vector<uint8_t*> outs(B);
+    for (int b = 0; b < B; ++b) {
+        (*parity)[b].resize(lens[b] % static_cast<size_t>(k_) == 0 ? lens[b] / static_cast<size_t>(k_) * (n_ - k_) : 0);
+        outs[b] = (*parity)[b].data();
+    }
+    std::vector<int> codes(B, RS_OK);
+    const int rc = rs_encode_batch_lens(ctx_, B, inputs.data(), lens.data(), outs.data(), codes.data());
+    for (int b = 0; b < B; ++b)
+        if (codes[b] != RS_OK) {
+            (*st)[b] = from(codes[b], "Encode");
+            (*parity)[b].clear();
+        }
+    return rc == RS_OK ? Status::Ok() : from(rc, "EncodeBatchLens");
+}
+
 Status FEC::Decode(std::vector<uint8_t>* dst, std::vector<Share>& shares) {
     const int cnt = static_cast<int>(shares.size());
     const size_t S = cnt ? shares[0].Data.size() : 0;
@@ -108,25 +130,28 @@ Status FEC::DecodeBatch(std::vector<std::vector<Share>>& msgs, std::vector<std::
     out->assign(B, {});
     st->assign(B, Status::Ok());
     if (B == 0) return Status::Ok();
-    const size_t S = msgs[0].empty() ? 0 : msgs[0][0].Data.size();
+    // A share length per message (rs_decode_batch_lens; with one length for
+    // all it is rs_decode_batch); the shares of one message must agree.
+    std::vector<size_t> S(B);
     std::vector<int> counts(B), nums;
     std::vector<const uint8_t*> ptrs;
     for (int b = 0; b < B; ++b) {
+        S[b] = msgs[b].empty() ? 0 : msgs[b][0].Data.size();
         counts[b] = static_cast<int>(msgs[b].size());
         for (const Share& s : msgs[b]) {
-            if (s.Data.size() != S) return from(RS_ESHARE_LEN, "DecodeBatch");
+            if (s.Data.size() != S[b]) return from(RS_ESHARE_LEN, "DecodeBatch");
             nums.push_back(s.Number);
             ptrs.push_back(s.Data.data());
         }
     }
     std::vector<uint8_t*> dsts(B);
     for (int b = 0; b < B; ++b) {
-        (*out)[b].resize(static_cast<size_t>(k_) * S);
+        (*out)[b].resize(static_cast<size_t>(k_) * S[b]);
         dsts[b] = (*out)[b].data();
     }
     std::vector<int> codes(B, 0);
-    const int rc = rs_decode_batch(ctx_, B, counts.data(), nums.data(), ptrs.data(), S, dsts.data(),
-                                   codes.data());
+    const int rc = rs_decode_batch_lens(ctx_, B, counts.data(), nums.data(), ptrs.data(), S.data(), dsts.data(),
+                                        codes.data());
     for (int b = 0; b < B; ++b) {
         if (codes[b] != RS_OK) {
             (*st)[b] = from(codes[b], "Decode");
@@ -166,25 +191,26 @@ Status FEC::DecodeBatchShared(const std::vector<std::vector<std::shared_ptr<cons
     out->assign(B, {});
     st->assign(B, Status::Ok());
     if (B == 0) return Status::Ok();
-    const size_t S = msgs[0].empty() ? 0 : msgs[0][0]->Data.size();
+    std::vector<size_t> S(B);  // a share length per message, as DecodeBatch
     std::vector<int> counts(B), nums;
     std::vector<const uint8_t*> ptrs;
     for (int b = 0; b < B; ++b) {
+        S[b] = msgs[b].empty() ? 0 : msgs[b][0]->Data.size();
         counts[b] = static_cast<int>(msgs[b].size());
         for (const std::shared_ptr<const Share>& s : msgs[b]) {
-            if (s->Data.size() != S) return from(RS_ESHARE_LEN, "DecodeBatch");
+            if (s->Data.size() != S[b]) return from(RS_ESHARE_LEN, "DecodeBatch");
             nums.push_back(s->Number);
             ptrs.push_back(s->Data.data());
         }
     }
     std::vector<uint8_t*> dsts(B);
     for (int b = 0; b < B; ++b) {
-        (*out)[b].resize(static_cast<size_t>(k_) * S);
+        (*out)[b].resize(static_cast<size_t>(k_) * S[b]);
         dsts[b] = (*out)[b].data();
     }
     std::vector<int> codes(B, 0);
-    const int rc = rs_decode_batch(ctx_, B, counts.data(), nums.data(), ptrs.data(), S, dsts.data(),
-                                   codes.data());
+    const int rc = rs_decode_batch_lens(ctx_, B, counts.data(), nums.data(), ptrs.data(), S.data(), dsts.data(),
+                                        codes.data());
     for (int b = 0; b < B; ++b)
         if (codes[b] != RS_OK) {
             (*st)[b] = from(codes[b], "Decode");

@@ -62,10 +62,17 @@ public:
     // inputs[b] (rs_encode's layout), (*st)[b] its status.
     Status EncodeBatch(const std::vector<const uint8_t*>& inputs, size_t len,
                        std::vector<std::vector<uint8_t>>* parity, std::vector<Status>* st);
+    // The same for messages of their own lengths, inputs[b] of lens[b] bytes
+    // (rs_encode_batch_lens): a length that is no multiple of k fails that
+    // message alone.
+    Status EncodeBatchLens(const std::vector<const uint8_t*>& inputs, const std::vector<size_t>& lens,
+                           std::vector<std::vector<uint8_t>>* parity, std::vector<Status>* st);
     // Sorts `shares` by Number in place; *dst receives k * len(share) bytes.
     Status Decode(std::vector<uint8_t>* dst, std::vector<Share>& shares);
-    // Decode of many messages (same share length) in one GPU pass
-    // (rs_decode_batch); (*out)[b] / (*st)[b] per message.
+    // Decode of many messages in one call (rs_decode_batch_lens: one GPU pass
+    // per staging group; rs_decode_batch when all share one length); the
+    // share length may differ from message to message, not within one
+    // (RS_ESHARE_LEN).  (*out)[b] / (*st)[b] per message.
     Status DecodeBatch(std::vector<std::vector<Share>>& msgs, std::vector<std::vector<uint8_t>>* out,
                        std::vector<Status>* st);
     // The same over shares held by shared ownership (the plugin's mempool

@@ -5,6 +5,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "../../include/rsmi.h"
 #include "infectious.hpp"
 #include "plugin_latency.hpp"
 #include "shard_plugin.hpp"
@@ -80,6 +81,29 @@ PYBIND11_MODULE(_rsmi_host, m) {
                      res.append(st[b].ok() ? py::object(to_bytes(par[b])) : py::object(py::none()));
                  return res;
              })
+        .def("EncodeBatchLens",
+             [](FEC& f, const std::vector<py::bytes>& inputs) {
+                 // messages of any lengths (rs_encode_batch_lens); None where a message failed
+                 std::vector<std::string> keep(inputs.begin(), inputs.end());
+                 std::vector<const uint8_t*> ptrs;
+                 std::vector<size_t> lens;
+                 for (const std::string& x : keep) {
+                     ptrs.push_back(reinterpret_cast<const uint8_t*>(x.data()));
+                     lens.push_back(x.size());
+                 }
+                 std::vector<std::vector<uint8_t>> par;
+                 std::vector<Status> st;
+                 {
+                     py::gil_scoped_release nogil;
+                     f.EncodeBatchLens(ptrs, lens, &par, &st);
+                 }
+                 py::list res;
+                 for (size_t b = 0; b < par.size(); ++b)
+                     res.append(st[b].ok() ? py::object(to_bytes(par[b])) : py::object(py::none()));
+                 return res;
+             })
+        // rs_stat of the engine context behind the FEC (diagnostics / tests)
+        .def("Stat", [](const FEC& f, int which) { return rs_stat(f.ctx(), which); })
         .def("DecodeBatch",
              [](FEC& f, std::vector<std::vector<Share>> msgs) {
                  std::vector<std::vector<uint8_t>> outs;
@@ -96,6 +120,12 @@ PYBIND11_MODULE(_rsmi_host, m) {
             return py::make_tuple(to_bytes(out), shares);
         });
 
+    // The process-wide FEC of (k, n) that the plugins encode and decode with.
+    m.def("CachedFEC", [](int k, int n) {
+        std::shared_ptr<FEC> f;
+        check(CachedFEC(k, n, &f));
+        return f;
+    });
     m.def("NewFEC", [](int k, int n) {
         std::shared_ptr<FEC> f;
         check(NewFEC(k, n, &f));

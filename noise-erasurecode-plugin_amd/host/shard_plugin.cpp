@@ -209,41 +209,41 @@ void ShardPlugin::prepareShardsBatch(const PeerID& self, const std::vector<std::
         }
         for (size_t i = 0; i < inputs.size(); ++i) sigs[i] = sign_(h[i]);
     }
-    // The encodes: messages of equal length go through one rs_encode_batch
-    // pass each (send-side batching); then shardInput's shares per message
-    // (data shares copied out of the input, main.go:255-258).
+    // The encodes: all messages, whatever their lengths, go through one
+    // rs_encode_batch_lens call (send-side batching); then shardInput's
+    // shares per message (data shares copied out of the input,
+    // main.go:255-258).
     std::shared_ptr<FEC> f;
     Status fs = CachedFEC(MinimumNeededShards, TotalShards, &f);
     if (!fs.ok()) {
         sts->assign(inputs.size(), fs);
         return;
     }
-    std::map<size_t, std::vector<size_t>> by_len;
-    for (size_t i = 0; i < inputs.size(); ++i) by_len[inputs[i].size()].push_back(i);
     const size_t k = static_cast<size_t>(MinimumNeededShards), m = static_cast<size_t>(TotalShards) - k;
-    for (const auto& [len, idx] : by_len) {
-        std::vector<const uint8_t*> ptrs;
-        for (size_t i : idx) ptrs.push_back(inputs[i].data());
-        std::vector<std::vector<uint8_t>> parity;
-        std::vector<Status> est;
-        f->EncodeBatch(ptrs, len, &parity, &est);
-        for (size_t q = 0; q < idx.size(); ++q) {
-            const size_t i = idx[q];
-            if (!est[q].ok()) {
-                (*sts)[i] = est[q];
-                continue;
-            }
-            const size_t S = len / k;
-            for (size_t sn = 0; sn < k + m; ++sn) {
-                Shard sh;
-                sh.FileSignature = sigs[i];
-                const uint8_t* src = sn < k ? inputs[i].data() + sn * S : parity[q].data() + (sn - k) * S;
-                sh.ShardData.assign(src, src + S);
-                sh.ShardNumber = static_cast<uint64_t>(sn);
-                sh.TotalShards = static_cast<uint64_t>(TotalShards);
-                sh.MinimumNeededShards = static_cast<uint64_t>(MinimumNeededShards);
-                (*out)[i].push_back(std::move(sh));
-            }
+    std::vector<const uint8_t*> ptrs;
+    std::vector<size_t> lens;
+    for (const std::vector<uint8_t>& in : inputs) {
+        ptrs.push_back(in.data());
+        lens.push_back(in.size());
+    }
+    std::vector<std::vector<uint8_t>> parity;
+    std::vector<Status> est;
+    f->EncodeBatchLens(ptrs, lens, &parity, &est);
+    for (size_t i = 0; i < inputs.size(); ++i) {
+        if (!est[i].ok()) {
+            (*sts)[i] = est[i];
+            continue;
+        }
+        const size_t S = lens[i] / k;
+        for (size_t sn = 0; sn < k + m; ++sn) {
+            Shard sh;
+            sh.FileSignature = sigs[i];
+            const uint8_t* src = sn < k ? inputs[i].data() + sn * S : parity[i].data() + (sn - k) * S;
+            sh.ShardData.assign(src, src + S);
+            sh.ShardNumber = static_cast<uint64_t>(sn);
+            sh.TotalShards = static_cast<uint64_t>(TotalShards);
+            sh.MinimumNeededShards = static_cast<uint64_t>(MinimumNeededShards);
+            (*out)[i].push_back(std::move(sh));
         }
     }
 }
@@ -428,34 +428,42 @@ void ShardPlugin::ReceiveBatch(const std::vector<std::pair<PeerID, Shard>>& msgs
             }
         };
         std::vector<size_t> verify_jobs;
-        // Decode the phase's pools, grouped by (k, n, share length).
-        std::map<std::tuple<uint64_t, uint64_t, size_t>, std::vector<size_t>> groups;
+        // Decode the phase's pools, grouped by (k, n): the share length may
+        // differ from pool to pool (rs_decode_batch_lens).
+        std::map<std::pair<uint64_t, uint64_t>, std::vector<size_t>> groups;
         for (size_t j = 0; j < jobs.size(); ++j) {
             const Shard& m = msgs[jobs[j].msg].second;
-            const size_t S = jobs[j].pool.empty() ? 0 : jobs[j].pool[0]->Data.size();
-            groups[{m.MinimumNeededShards, m.TotalShards, S}].push_back(j);
+            groups[{m.MinimumNeededShards, m.TotalShards}].push_back(j);
         }
         for (auto& g : groups) {
             std::vector<size_t>& ids = g.second;
             for (size_t j : ids) (*evs)[jobs[j].msg].decoded = true;
             std::shared_ptr<FEC> f;
-            Status fs = CachedFEC(static_cast<int>(std::get<0>(g.first)),
-                                  static_cast<int>(std::get<1>(g.first)), &f);
+            Status fs = CachedFEC(static_cast<int>(g.first.first), static_cast<int>(g.first.second), &f);
+            std::vector<std::vector<uint8_t>> outs(ids.size());
+            std::vector<Status> st(ids.size(), fs);
+            // A pool whose own shares differ in length goes alone; the others
+            // in one batch.
+            std::vector<size_t> batched;  // positions in ids
             std::vector<std::vector<PoolEntry>> pools;
-            std::vector<std::vector<uint8_t>> outs;
-            std::vector<Status> st;
-            bool uniform = true;  // a pool with mixed share lengths goes alone
-            for (size_t j : ids)
-                for (const PoolEntry& s : jobs[j].pool) uniform &= s->Data.size() == std::get<2>(g.first);
-            if (fs.ok() && uniform) {
-                for (size_t j : ids) pools.push_back(jobs[j].pool);
-                f->DecodeBatchShared(pools, &outs, &st);
-            } else {
-                for (size_t j : ids) {
-                    std::vector<uint8_t> o;
-                    Status s1 = fs.ok() ? f->DecodeShared(&o, jobs[j].pool) : fs;
-                    outs.push_back(std::move(o));
-                    st.push_back(s1);
+            for (size_t q = 0; fs.ok() && q < ids.size(); ++q) {
+                const std::vector<PoolEntry>& pool = jobs[ids[q]].pool;
+                bool uniform = true;
+                for (const PoolEntry& s : pool) uniform &= s->Data.size() == pool[0]->Data.size();
+                if (uniform) {
+                    batched.push_back(q);
+                    pools.push_back(pool);
+                } else {
+                    st[q] = f->DecodeShared(&outs[q], pool);
+                }
+            }
+            if (!batched.empty()) {
+                std::vector<std::vector<uint8_t>> bouts;
+                std::vector<Status> bst;
+                f->DecodeBatchShared(pools, &bouts, &bst);  // every pool is uniform: a status per message
+                for (size_t v = 0; v < batched.size(); ++v) {
+                    st[batched[v]] = bst[v];
+                    outs[batched[v]] = std::move(bouts[v]);
                 }
             }
             for (size_t q = 0; q < ids.size(); ++q) {

@@ -104,7 +104,8 @@ public:
     // Receive for a batch of arrivals (receive-side batching, SURVEY.md §8f
     // rank 3): the same pooling rules and per-key order as calling Receive on
     // each message in turn, but every pool that triggers in a phase is
-    // decoded in one GPU pass (FEC::DecodeBatch per (k, n, share length)).
+    // decoded in one call per (k, n) (FEC::DecodeBatchShared: the pools' share
+    // lengths may differ; a pool whose own shares differ goes alone).
     // Arrivals for a key whose decode is in flight wait for the next phase.
     // (*evs)[i] / (*sts)[i] correspond to msgs[i].
     void ReceiveBatch(const std::vector<std::pair<PeerID, Shard>>& msgs,
@@ -127,9 +128,9 @@ public:
     Status prepareShards(const PeerID& self, const std::vector<uint8_t>* input,
                          std::vector<Shard>* out);
     // prepareShards for many inputs: every input's signature hash in one
-    // rs_blake2b call (HashLen > 0), and the encodes of equal-length inputs
-    // in one rs_encode_batch pass each (send-side batching); shares as
-    // shardInput makes them.  (*out)[i] / (*sts)[i] correspond to inputs[i].
+    // rs_blake2b call (HashLen > 0), and the encodes of all inputs, whatever
+    // their lengths, in one rs_encode_batch_lens call (send-side batching);
+    // shares as shardInput makes them.  (*out)[i] / (*sts)[i] correspond to inputs[i].
     void prepareShardsBatch(const PeerID& self, const std::vector<std::vector<uint8_t>>& inputs,
                             std::vector<std::vector<Shard>>* out, std::vector<Status>* sts);
     // main.go:243-267

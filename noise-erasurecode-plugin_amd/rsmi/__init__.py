@@ -40,6 +40,7 @@ EXPORTS = (
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
+    "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
     "rs_pattern_survivors",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
@@ -154,6 +155,10 @@ def _lib() -> ctypes.CDLL:
             "rs_decode_batch": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32),
                                       ctypes.POINTER(vp), sz, ctypes.POINTER(vp), ctypes.POINTER(i32)]),
             "rs_encode_batch": (i32, [vp, i32, ctypes.POINTER(vp), sz, ctypes.POINTER(vp), ctypes.POINTER(i32)]),
+            "rs_encode_batch_lens": (i32, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp),
+                                           ctypes.POINTER(i32)]),
+            "rs_decode_batch_lens": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                           ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(i32)]),
             "rs_encode_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp]),
             "rs_reconstruct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_reconstruct_ptrs": (i32, [vp, vp, sz, sz, vp, vp]),
@@ -166,6 +171,7 @@ def _lib() -> ctypes.CDLL:
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
+            "rs_combine_lens": (i32, [vp, ctypes.POINTER(CombineJob), sz, ctypes.POINTER(sz), vp]),
             "rs_pattern_survivors": (i32, [vp, vp, ctypes.POINTER(i32)]),
             "rs_pattern_count": (i32, [vp]),
             "rs_pattern_evictions": (ctypes.c_int64, [vp]),
@@ -334,7 +340,8 @@ class FEC:
     def kernel_name(self, which: int = 0) -> str:
         """Kernel serving encode (0), reconstruct (1), verify (2), update
         (3), degraded read (4), degraded check (5), combine (6), degraded
-        update (7) or column scrub (8): diagnostics."""
+        update (7), column scrub (8) or combine_lens of mixed lengths (9):
+        diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -440,6 +447,53 @@ class FEC:
         st = (ctypes.c_int * max(B, 1))()
         _lib().rs_encode_batch(self._h, B, ins, L, outp, st)
         return ([bytes(o[:P]) if st[b] == RS_OK else None for b, o in enumerate(outs)],
+                [st[b] for b in range(B)])
+
+    def EncodeBatchLens(self, inputs: List[bytes]):
+        """rs_encode_batch_lens: EncodeBatch for messages of any lengths, in
+        one call.  Returns (parities, statuses); a message whose length is no
+        multiple of k fails alone."""
+        B = len(inputs)
+        m = self.n - self.k
+        P = [(len(x) // self.k) * m if len(x) % self.k == 0 else 0 for x in inputs]
+        keep = [bytes(x) for x in inputs]
+        ins = (ctypes.c_void_p * max(B, 1))(
+            *[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value for b in keep])
+        lens = (ctypes.c_size_t * max(B, 1))(*[len(x) for x in keep])
+        outs = [bytearray(max(p, 1)) for p in P]
+        outp = (ctypes.c_void_p * max(B, 1))(
+            *[ctypes.addressof((ctypes.c_char * len(o)).from_buffer(o)) for o in outs])
+        st = (ctypes.c_int * max(B, 1))()
+        _lib().rs_encode_batch_lens(self._h, B, ins, lens, outp, st)
+        return ([bytes(o[:P[b]]) if st[b] == RS_OK else None for b, o in enumerate(outs)],
+                [st[b] for b in range(B)])
+
+    def DecodeBatchLens(self, messages: List[List[Share]]):
+        """rs_decode_batch_lens: DecodeBatch for messages of different share
+        lengths, in one call; the shares of one message must still agree.
+        Sorts each message's list in place by Number, as Decode does.  Returns
+        (outputs, statuses); outputs[b] is None where statuses[b] != 0."""
+        B = len(messages)
+        S = [len(msg[0].Data) if msg else 0 for msg in messages]
+        for msg, length in zip(messages, S):
+            for s in msg:
+                if len(s.Data) != length:
+                    raise RSError(RS_ESHARE_LEN, "DecodeBatchLens")
+        counts = (ctypes.c_int * max(B, 1))(*[len(msg) for msg in messages])
+        flat = [s for msg in messages for s in msg]
+        nums = (ctypes.c_int * max(len(flat), 1))(*[s.Number for s in flat])
+        keep = [bytes(s.Data) for s in flat]
+        ptrs = (ctypes.c_void_p * max(len(flat), 1))(
+            *[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value for b in keep])
+        lens = (ctypes.c_size_t * max(B, 1))(*S)
+        outs = [bytearray(max(self.k * length, 1)) for length in S]
+        outp = (ctypes.c_void_p * max(B, 1))(
+            *[ctypes.addressof((ctypes.c_char * max(len(o), 1)).from_buffer(o)) for o in outs])
+        st = (ctypes.c_int * max(B, 1))()
+        _lib().rs_decode_batch_lens(self._h, B, counts, nums, ptrs, lens, outp, st)
+        for msg in messages:  # mirror the in-place sort
+            msg.sort(key=lambda s: s.Number)
+        return ([bytes(o[:self.k * S[b]]) if st[b] == RS_OK else None for b, o in enumerate(outs)],
                 [st[b] for b in range(B)])
 
     # -- device-resident batched API -------------------------------------------
@@ -603,6 +657,17 @@ class FEC:
         arr = jobs if isinstance(jobs, ctypes.Array) else combine_jobs(jobs)
         _check(_lib().rs_combine(self._h, arr, arr._count, length, stream or None), "rs_combine")
 
+    def combine_lens(self, jobs: Sequence[tuple], lengths: Sequence[int], stream: int = 0) -> None:
+        """rs_combine_lens: combine() with job b over buffers of lengths[b]
+        bytes; a job of length 0 does nothing.  A caller that repeats a large
+        list passes a ctypes c_size_t array of the lengths, as it passes the
+        table of combine_jobs().  Enqueued on stream."""
+        arr = jobs if isinstance(jobs, ctypes.Array) else combine_jobs(jobs)
+        if len(lengths) != arr._count:
+            raise RSError(RS_EINVAL, "lengths must hold one length per job")
+        lens = lengths if isinstance(lengths, ctypes.Array) else (ctypes.c_size_t * max(len(lengths), 1))(*lengths)
+        _check(_lib().rs_combine_lens(self._h, arr, arr._count, lens, stream or None), "rs_combine_lens")
+
     def pattern_survivors(self, erased: bytes) -> List[int]:
         """The shard id behind each of the k columns of pattern_rows(erased)."""
         if len(erased) != self.n:
@@ -634,7 +699,8 @@ class FEC:
      STAT_ENCODE_BATCHES, STAT_MAILBOX_CALLS, STAT_MAILBOX_RECOVERED, STAT_UPDATE_STRIPES,
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
-     STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES) = range(24)
+     STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES, STAT_BATCH_LENS_PASSES,
+     STAT_COMBINE_LENS_LAUNCHES) = range(26)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
