@@ -82,7 +82,10 @@ const char *rs_strerror(int status);
  * reference counterpart); which = 8: the rs_correct_columns variant, e.g.
  * "columns_MG4_B256", or "none" for a code the call does not serve; which =
  * 9: the per-job-length twin of which = 6 that serves rs_combine_lens calls of
- * mixed lengths, e.g. "combine_lens_MG4_B256". */
+ * mixed lengths, e.g. "combine_lens_MG4_B256"; which = 10 and 11: the
+ * pointer-mode twins of which = 5 and 8 that serve rs_verify_ptrs and
+ * rs_correct_columns_ptrs, e.g. "check_K10_MG4_B256_ptrs" and
+ * "columns_MG4_B256_ptrs". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -579,6 +582,39 @@ int rs_combine_lens(rs_ctx *ctx, const rs_combine_job *jobs, size_t count, const
 int rs_reconstruct_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
                         const uint8_t *erased, void *stream);
 
+/* The scrub of the pointer placement: shard_ptrs as for rs_reconstruct_ptrs
+ * (DEVICE, [stripes][n], 8-byte aligned, 16-byte-aligned addresses, only
+ * read), and "the slot of shard i of stripe s" is shard_ptrs[s * n + i].
+ * erased: HOST, stripes * n flags, non-zero = missing; NULL or no flag set =
+ * every shard present.  Table entries of erased shards may hold anything and
+ * are never dereferenced, for reading or writing;
+ * round_up(shard_len, 16) bytes of every present shard of a checked stripe
+ * are read.  Refused with nothing launched or written: RS_EINVAL for a NULL
+ * or misaligned table (or first_bad), shard_len of 2^28 or more 16-byte
+ * columns, stripes >= 2^32; RS_ENOT_ENOUGH when a stripe has more than m
+ * erasures.  RS_OK for stripes == 0 or shard_len == 0, and for m == 0 (every
+ * stripe RS_VERIFY_CLEAN).  Both count into RS_STAT_CHECK_STRIPES, the
+ * second into RS_STAT_COLUMN_STRIPES / RS_STAT_COLUMN_BYTES.
+ *
+ * rs_verify_ptrs is rs_verify_degraded (rs_verify_stripes when no flag is
+ * set) on that placement: first_bad (DEVICE, uint32[stripes]) and
+ * RS_VERIFY_CLEAN as there, a stripe with exactly m erasures is clean.  It
+ * only reads, so table entries may repeat.  Enqueued on stream; returns when
+ * queued.
+ *
+ * rs_correct_columns_ptrs is rs_correct_columns on that placement: the same
+ * per-column decoding within floor((r - k) / 2), status (HOST int[stripes])
+ * and corrected (HOST uint32[stripes * n]) as there, the same sequence
+ * (verify, one column launch over the inconsistent stripes, verify of those
+ * again), synchronous, RS_EINVAL for m > 16.  Bytes at offsets >= shard_len,
+ * clean stripes and the table are never written.  The caller guarantees
+ * (not checked: the table lives on the device) that the ranges of the
+ * present shards named by the table do not overlap each other. */
+int rs_verify_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
+                   const uint8_t *erased, uint32_t *first_bad, void *stream);
+int rs_correct_columns_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
+                            const uint8_t *erased, int *status, uint32_t *corrected, void *stream);
+
 /* Cached decode patterns held by the ctx (diagnostics / tests).  The cache
  * holds at most 2^20 patterns (RSMI_PATTERN_CAP); a call that would exceed
  * that evicts it whole, with no host synchronisation (the rebuilt rows wait
@@ -726,6 +762,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
  *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
+ *    rs_verify_ptrs, rs_correct_columns_ptrs,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

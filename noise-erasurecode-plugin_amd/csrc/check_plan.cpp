@@ -14,10 +14,12 @@ void clear(CheckPlan* plan) {
     plan->saturated = 0;
     plan->max_j = 0;
 }
-}  // namespace
 
-int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
-                const CheckLayout& lay, CheckPlan* plan) {
+// The planner of both placements: dst_of(stripe, id) is what an entry carries
+// for the stored shard `id` of `stripe`.
+template <class DstOf>
+int plan_impl(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count, DstOf dst_of,
+              CheckPlan* plan) {
     if (!plan) return RS_EINVAL;
     clear(plan);
     if (k < 1 || n < k || n > 256 || stripes > 0xFFFFFFFFull) return RS_EINVAL;
@@ -68,15 +70,28 @@ int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint3
         uint32_t rank = 0;
         for (int id = 0; id < n; ++id) {
             if (!xf[id]) continue;
-            if (!fl[id]) {
-                const uint64_t at = lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
-                                    static_cast<uint64_t>(id - k) * lay.pitch;
-                plan->entries.push_back(ReadEntry{at, rank, 0u});
-            }
+            if (!fl[id]) plan->entries.push_back(ReadEntry{dst_of(stripe, id), rank, 0u});
             ++rank;
         }
     }
     return RS_OK;
+}
+}  // namespace
+
+int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                const CheckLayout& lay, CheckPlan* plan) {
+    return plan_impl(k, n, stripes, erased, list, count,
+                     [&](uint32_t stripe, int id) {
+                         return lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
+                                static_cast<uint64_t>(id - k) * lay.pitch;
+                     },
+                     plan);
+}
+
+int plan_checks_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                     CheckPlan* plan) {
+    return plan_impl(k, n, stripes, erased, list, count,
+                     [](uint32_t, int id) { return static_cast<uint64_t>(id); }, plan);
 }
 
 }  // namespace rsmi

@@ -30,7 +30,8 @@ struct CheckPlan {
     std::vector<uint32_t> intact;    // stripes without erasures, increasing: the verify kernel's
     std::vector<ReadJob> jobs;       // one per degraded stripe, in stripe order
     std::vector<ReadEntry> entries;  // a job's entries are its shards of U in id order:
-                                     // {dst = address of the stored shard, row = rank of the id in X'}
+                                     // {dst = address of the stored shard (plan_checks_ptrs: its
+                                     // id), row = rank of the id in X'}
     std::vector<uint8_t> flags;      // [jobs.size()][n]: X' of every job, 0 / 1
     size_t saturated = 0;            // stripes with exactly m erasures (and m > 0): nothing to check
     uint32_t max_j = 0;              // the largest j = m - e of any job
@@ -46,5 +47,14 @@ struct CheckPlan {
 //   RS_ENOT_ENOUGH  a planned stripe has more than n - k erasures
 int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
                 const CheckLayout& lay, CheckPlan* plan);
+
+// The same plan for the pointer placement (rs_verify_ptrs,
+// rs_correct_columns_ptrs), where shard i of stripe s is at the device table's
+// shard_ptrs[s * n + i] and the host knows no address: an entry's dst is the
+// shard ID of the stored shard, which the check kernel resolves through the
+// table.  Everything else -- the splits, the jobs, the rows, the flags, the
+// refusals -- is plan_checks'.
+int plan_checks_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                     CheckPlan* plan);
 
 }  // namespace rsmi

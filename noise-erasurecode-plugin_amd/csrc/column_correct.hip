@@ -36,7 +36,26 @@ static_assert(kColSources * kColumnMaxSyn * 5 * 4 <= kColRegion, "tables fit the
 // {block, shard}: a wholly wrong shard is 4,096 corrected bytes per block on
 // one counter.
 // LDS: exp [512] | log [256] | ids, x, u [256] each | counts u32 [256] | the shared region.
-template <int MG>
+//
+// PTRS (compile-time twin, the pointer placement): shard id of the stripe is at
+// a.shard_ptrs[stripe * n + id].  The block resolves the addresses of the r
+// present shards once, next to the ids, into 2 KiB more of LDS indexed by the
+// shard's position in the present list: phase A's loads and phase B's byte
+// stores read that array, never the table, and the table entries of shards
+// outside the present list are never loaded.
+
+// The twin's address array; only the PTRS instantiations allocate it.
+template <bool PTRS>
+__device__ __forceinline__ uint64_t* column_ptr_lds() {
+    if constexpr (PTRS) {
+        __shared__ uint64_t s_ptr[256];
+        return s_ptr;
+    } else {
+        return nullptr;
+    }
+}
+
+template <int MG, bool PTRS = false>
 __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
@@ -59,15 +78,23 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
     for (int i = tid; i < 512; i += kColBlock) s_exp[i] = a.gf[i];
     s_log[tid] = a.gf[512 + tid];
     s_cnt[tid] = 0u;
+    uint64_t* s_ptr = column_ptr_lds<PTRS>();
     if (tid < r) {
-        s_ids[tid] = tab[tid];
+        const uint8_t id = tab[tid];
+        s_ids[tid] = id;
         s_x[tid] = tab[np + tid];
         s_u[tid] = tab[2u * np + tid];
+        if constexpr (PTRS) s_ptr[tid] = a.shard_ptrs[stripe * a.n + id];
     }
 
-    auto slot = [&](uint32_t id) -> uint8_t* {
-        return id < a.k ? a.data + stripe * a.data_ss + static_cast<uint64_t>(id) * a.pitch
-                        : a.parity + stripe * a.parity_ss + static_cast<uint64_t>(id - a.k) * a.pitch;
+    // Shard `id`, the pos-th of the present list.
+    auto slot = [&](int pos, uint32_t id) -> uint8_t* {
+        if constexpr (PTRS) {
+            return reinterpret_cast<uint8_t*>(s_ptr[pos]);
+        } else {
+            return id < a.k ? a.data + stripe * a.data_ss + static_cast<uint64_t>(id) * a.pitch
+                            : a.parity + stripe * a.parity_ss + static_cast<uint64_t>(id - a.k) * a.pitch;
+        }
     };
     const uint32_t col = chunk * kColBlock + static_cast<uint32_t>(tid);
     const bool ok = col < a.ncols16;
@@ -95,8 +122,18 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
 #pragma unroll
             for (int q = 0; q < kColLoads; ++q) {
                 if (q0 + q >= cnt) break;
-                const uint32_t id = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(s_ids[i0 + q0 + q]));
-                x[q] = *reinterpret_cast<const uint4*>(slot(id) + off);
+                if constexpr (PTRS) {
+                    // Uniform: one LDS read, the base in SGPRs.  The halves go through
+                    // uint32_t: the builtin returns int, which would sign-extend the low word.
+                    const uint64_t at = s_ptr[i0 + q0 + q];
+                    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(at));
+                    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(at >> 32));
+                    const uint8_t* base = reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
+                    x[q] = *reinterpret_cast<const uint4*>(base + off);
+                } else {
+                    const uint32_t id = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(s_ids[i0 + q0 + q]));
+                    x[q] = *reinterpret_cast<const uint4*>(slot(i0 + q0 + q, id) + off);
+                }
             }
 #pragma unroll
             for (int q = 0; q < kColLoads; ++q) {
@@ -143,8 +180,9 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
             continue;
         }
         for (int e = 0; e < nu; ++e) {
-            const uint32_t id = s_ids[ws[kColumnWsPos + e]];
-            uint8_t* p = slot(id) + o;
+            const int pos = ws[kColumnWsPos + e];
+            const uint32_t id = s_ids[pos];
+            uint8_t* p = slot(pos, id) + o;
             *p ^= ws[kColumnWsX + e];
             atomicAdd(&s_cnt[id], 1u);
         }
@@ -169,6 +207,14 @@ hipError_t launch_column_correct(const ColArgs& a, int m, hipStream_t stream) {
     if (a.njobs == 0 || a.chunks == 0) return hipSuccess;
     if (!column_correct_supported(m)) return hipErrorInvalidValue;
     const dim3 grid(a.njobs * a.chunks), block(kColBlock);
+    if (a.shard_ptrs) {
+        switch (column_mg(m)) {
+            case 4: hipLaunchKernelGGL((rs_column_kernel<4, true>), grid, block, 0, stream, a); break;
+            case 8: hipLaunchKernelGGL((rs_column_kernel<8, true>), grid, block, 0, stream, a); break;
+            default: hipLaunchKernelGGL((rs_column_kernel<16, true>), grid, block, 0, stream, a); break;
+        }
+        return hipGetLastError();
+    }
     switch (column_mg(m)) {
         case 4: hipLaunchKernelGGL(rs_column_kernel<4>, grid, block, 0, stream, a); break;
         case 8: hipLaunchKernelGGL(rs_column_kernel<8>, grid, block, 0, stream, a); break;
@@ -183,6 +229,15 @@ const char* column_variant_name(int m) {
         case 4: return "columns_MG4_B256";
         case 8: return "columns_MG8_B256";
         default: return "columns_MG16_B256";
+    }
+}
+
+const char* column_ptrs_variant_name(int m) {
+    if (!column_correct_supported(m)) return "none";
+    switch (column_mg(m)) {
+        case 4: return "columns_MG4_B256_ptrs";
+        case 8: return "columns_MG8_B256_ptrs";
+        default: return "columns_MG16_B256_ptrs";
     }
 }
 

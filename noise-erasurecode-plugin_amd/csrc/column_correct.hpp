@@ -31,6 +31,10 @@ struct ColArgs {
     uint32_t* fail;         // [njobs] (device), zero at launch
     uint32_t njobs;
     uint32_t chunks;  // filled in by plan_column_correct
+    // Pointer placement: [stripe][n] device address of every shard (device, only
+    // read; data / parity / strides / pitch unused), or nullptr.  The kernel's
+    // pointer-mode twin loads the entries of the job's present shards only.
+    const uint64_t* shard_ptrs;
 };
 // Whether a code with m parity shards is served (1 <= m <= 16).
 bool column_correct_supported(int m);
@@ -38,5 +42,6 @@ bool column_correct_supported(int m);
 bool plan_column_correct(ColArgs* a);
 hipError_t launch_column_correct(const ColArgs& a, int m, hipStream_t stream);  // a: planned
 const char* column_variant_name(int m);  // "columns_MG4_B256" etc.; "none" for a code that is not served
+const char* column_ptrs_variant_name(int m);  // the pointer-mode twin: "columns_MG4_B256_ptrs" etc.
 
 }  // namespace rsmi

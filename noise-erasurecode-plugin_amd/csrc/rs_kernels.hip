@@ -1134,8 +1134,18 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
 // stored; the slots of erased shards are in neither the pattern's survivors
 // nor the entries, so no address into them is ever formed.
 // LDS: [k][20] table dwords | k survivor pointers.
-template <int K, int MG, int BT, bool NT>
-__global__ __launch_bounds__(BT) void rs_check_kernel(ReadArgs a, uint32_t* first_bad, uint32_t shard_len) {
+//
+// PTRS (compile-time twin, launch_check_ptrs): shard id of stripe s is at
+// a.shard_ptrs[s * n + id].  The survivors' addresses are one batch of scalar
+// loads from the table behind the batch of ids (K <= 16) or go to the LDS
+// pointer array; entries[..].dst is the stored shard's ID and is resolved
+// through the table too.  The table entries of erased shards are never loaded.
+struct CheckPtrArgs : ReadArgs {
+    const uint64_t* shard_ptrs;
+};
+template <int K, int MG, int BT, bool NT, bool PTRS = false>
+__global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, CheckPtrArgs, ReadArgs> a,
+                                                      uint32_t* first_bad, uint32_t shard_len) {
     extern __shared__ uint4 lds4[];
     static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
     constexpr bool kRegPtrs = K > 0 && K <= 16;           // survivor bases kept in SGPRs
@@ -1170,22 +1180,36 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(ReadArgs a, uint32_t* firs
     }
 
     const uint32_t* srcid = a.src + static_cast<size_t>(pat) * k;
-    uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
-    uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
     uint8_t* sp[kRegPtrs ? K : 1];
-    if constexpr (kRegPtrs) {
-        uint32_t ids[K];
+    const uint64_t* tp = nullptr;  // pointer mode: the stripe's row of the shard table
+    if constexpr (PTRS) {
+        tp = a.shard_ptrs + s * (a.k + a.m);
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
 #pragma unroll
-        for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
 #pragma unroll
-        for (int c = 0; c < K; ++c)
-            sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
-                                                     : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+            for (int c = 0; c < K; ++c) sp[c] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[ids[c]]));
+        } else {
+            for (int i = threadIdx.x; i < k; i += BT) sptr[i] = reinterpret_cast<uint8_t*>(tp[srcid[i]]);
+        }
     } else {
-        for (int i = threadIdx.x; i < k; i += BT) {
-            const uint32_t id = srcid[i];
-            sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
-                               : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+        uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
+        uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
+#pragma unroll
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+                sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
+                                                         : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+        } else {
+            for (int i = threadIdx.x; i < k; i += BT) {
+                const uint32_t id = srcid[i];
+                sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                                   : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+            }
         }
     }
     const uint32_t last = a.ncols16 - 1;
@@ -1201,8 +1225,18 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(ReadArgs a, uint32_t* firs
     }
     // Stored shards of the group's rows; rows past eg have none.
     const uint8_t* dp[MG];
+    if constexpr (PTRS) {
+        // The entries carry shard ids: all of them first, then their addresses.
+        uint32_t oid[MG];
 #pragma unroll
-    for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(ent[t].dst)) : nullptr;
+        for (int t = 0; t < MG; ++t)
+            oid[t] = t < eg ? __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(ent[t].dst)) : 0u;
+#pragma unroll
+        for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(tp[oid[t]])) : nullptr;
+    } else {
+#pragma unroll
+        for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(ent[t].dst)) : nullptr;
+    }
     // The accumulators start as the stored columns, loaded next to the
     // survivors so they ride the same latency.  Rows past eg are not read and
     // stay zero (they are not multiplied either, so they never report).
@@ -1584,8 +1618,12 @@ struct CheckVariant {
     int K;
     const char* name;
     void (*fn)(ReadArgs, uint32_t*, uint32_t);
+    const char* ptrs_name;  // the pointer-mode twin
+    void (*ptrs_fn)(CheckPtrArgs, uint32_t*, uint32_t);
 };
-#define RS_CHECK(K) {K, "check_K" #K "_MG4_B256", rs_check_kernel<K, 4, kBlock, true>}
+#define RS_CHECK(K)                                                                                    \
+    {K, "check_K" #K "_MG4_B256", rs_check_kernel<K, 4, kBlock, true>, "check_K" #K "_MG4_B256_ptrs", \
+     rs_check_kernel<K, 4, kBlock, true, true>}
 const CheckVariant kCheck[] = {RS_CHECK(10), RS_CHECK(4), RS_CHECK(8), RS_CHECK(64), RS_CHECK(0)};
 #undef RS_CHECK
 
@@ -1603,6 +1641,8 @@ const char* read_variant_name(int k) { return pick_read(k).name; }
 
 const char* check_variant_name(int k) { return pick_check(k).name; }
 
+const char* check_ptrs_variant_name(int k) { return pick_check(k).ptrs_name; }
+
 hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
     if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
     const CheckVariant& v = pick_check(static_cast<int>(a.k));
@@ -1610,6 +1650,22 @@ hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_l
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a, first_bad, shard_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad, uint32_t shard_len,
+                             hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    if (!shard_ptrs) return hipErrorInvalidValue;
+    const CheckVariant& v = pick_check(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    CheckPtrArgs pa{};
+    static_cast<ReadArgs&>(pa) = a;
+    pa.shard_ptrs = shard_ptrs;
+    hipLaunchKernelGGL(v.ptrs_fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, pa, first_bad,
+                       shard_len);
     return hipGetLastError();
 }
 

@@ -280,6 +280,16 @@ const char* read_variant_name(int k);  // "read_K10_MG4_B256" etc.
 hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream);  // a: planned
 const char* check_variant_name(int k);  // "check_K10_MG4_B256" etc.
 
+// The degraded check of the pointer placement (rs_verify_ptrs): shard i of
+// stripe s is at shard_ptrs[s * (k + m) + i] (device table, only read) and the
+// layout fields of `a` are unused.  The survivors' addresses come from the
+// table, and entries[..].dst holds the shard ID of the stored shard
+// (plan_checks_ptrs), resolved through the table as well.  A compile-time twin
+// of the check kernel: the strided instantiations keep their code.
+hipError_t launch_check_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad, uint32_t shard_len,
+                             hipStream_t stream);  // a: planned
+const char* check_ptrs_variant_name(int k);  // "check_K10_MG4_B256_ptrs" etc.
+
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard
 // id, for every shard of the stripe (a: strided layout, k, m).

@@ -1177,14 +1177,16 @@ int reconstruct_host_table(rs_ctx* c, const uint64_t* tab, size_t len, size_t st
 // Verify launch on stream s: first_bad[0 .. stripes) is preset to
 // RS_VERIFY_CLEAN, then the verify twin of the split-table encode kernel
 // checks every stripe (desc == nullptr) or the `count` stripes listed in desc
-// (device, {stripe index, 0 << 8 | m}).
+// (device, {stripe index, 0 << 8 | m}).  shard_ptrs: pointer mode, the
+// [stripes][n] shard address table in device memory (v = StripeView::ptrs).
 int launch_verify_stripes(const rs_ctx* c, const StripeView& v, size_t stripes, const uint2* desc, size_t count,
-                          uint32_t* first_bad, hipStream_t s) {
+                          uint32_t* first_bad, hipStream_t s, const uint64_t* shard_ptrs = nullptr) {
     if (hipMemsetAsync(first_bad, 0xFF, stripes * sizeof(uint32_t), s) != hipSuccess) return RS_EDEVICE;
     if (c->m == 0 || count == 0) return RS_OK;
     rsmi::MatArgs a = base_args(c, v, count);
     set_patterns(c, 1, c->d_encpat.p, a);
     a.stripe_desc = desc;
+    a.shard_ptrs = shard_ptrs;
     a.xcd = c->xcd_split_enc;
     return hip_status(rsmi::launch_verify(a, first_bad, static_cast<uint32_t>(v.len), s));
 }
@@ -1397,9 +1399,10 @@ int read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan&
 // to the device in one upload (upload_tables; a plan of saturated stripes only
 // has nothing to upload); then first_bad's preset and the verify kernel over
 // the intact stripes (launch_verify_stripes), then the check kernel over the
-// degraded ones.
+// degraded ones.  shard_ptrs: pointer mode (the plan is plan_checks_ptrs'),
+// as launch_verify_stripes.
 int launch_check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const rsmi::CheckPlan& plan,
-                         rsmi::ReadArgs a, uint32_t* first_bad, hipStream_t s) {
+                         rsmi::ReadArgs a, const uint64_t* shard_ptrs, uint32_t* first_bad, hipStream_t s) {
     const size_t nintact = plan.intact.size(), njobs = plan.jobs.size(), count = plan.entries.size();
     const size_t job_off = round_up(nintact * sizeof(uint2), 16);
     const size_t ent_off = job_off + njobs * sizeof(rsmi::ReadJob);
@@ -1415,14 +1418,16 @@ int launch_check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripe
         std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
     });
     if (up != RS_OK) return up;
-    int rc = launch_verify_stripes(c, v, stripes, reinterpret_cast<const uint2*>(t.dev), nintact, first_bad, s);
+    int rc = launch_verify_stripes(c, v, stripes, reinterpret_cast<const uint2*>(t.dev), nintact, first_bad, s,
+                                   shard_ptrs);
     if (rc == RS_OK && njobs > 0) {
         a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
         a.src = static_cast<const uint32_t*>(c->d_psrc.p);
         a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev + job_off);
         a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
         a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
-        rc = hip_status(rsmi::launch_check(a, first_bad, static_cast<uint32_t>(v.len), s));
+        rc = hip_status(shard_ptrs ? rsmi::launch_check_ptrs(a, shard_ptrs, first_bad, static_cast<uint32_t>(v.len), s)
+                                   : rsmi::launch_check(a, first_bad, static_cast<uint32_t>(v.len), s));
     }
     if (rc == RS_OK) c->check_stripes += static_cast<int64_t>(njobs);
     return finish_launch(c, L, s, t.waited, rc);
@@ -1433,15 +1438,23 @@ int launch_check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripe
 // rs_reconstruct_stripes fills (with_patterns; a plan without jobs takes no
 // lock).
 int check_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const rsmi::CheckPlan& plan,
-                  uint32_t* first_bad, hipStream_t s) {
+                  const uint64_t* shard_ptrs, uint32_t* first_bad, hipStream_t s) {
     rsmi::ReadArgs a = read_args(c, v, plan.jobs.size());
     if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
     return with_patterns(c, L, plan.flags.data(), plan.jobs.size(), s,
-                         [&] { return launch_check_stripes(c, L, v, stripes, plan, a, first_bad, s); });
+                         [&] { return launch_check_stripes(c, L, v, stripes, plan, a, shard_ptrs, first_bad, s); });
 }
 
 rsmi::CheckLayout check_layout(const StripeView& v) {
     return {reinterpret_cast<uintptr_t>(v.data), reinterpret_cast<uintptr_t>(v.parity), v.dss, v.pss, v.pitch};
+}
+
+// The check plan of a view: plan_checks for the strided layout, its sibling
+// for the pointer placement (shard_ptrs != nullptr).
+int plan_view_checks(const rs_ctx* c, const StripeView& v, const uint64_t* shard_ptrs, size_t stripes,
+                     const uint8_t* erased, const uint32_t* list, size_t count, rsmi::CheckPlan* plan) {
+    return shard_ptrs ? rsmi::plan_checks_ptrs(c->k, c->n, stripes, erased, list, count, plan)
+                      : rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), plan);
 }
 
 // ------------------------------------------------------ degraded update ----
@@ -1595,7 +1608,7 @@ int scrub_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, cons
         int rc;
         if (erased) {
             rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), &cp);
-            if (rc == RS_OK) rc = check_stripes(c, L, v, stripes, cp, d_fb, s);
+            if (rc == RS_OK) rc = check_stripes(c, L, v, stripes, cp, nullptr, d_fb, s);
         } else {
             for (size_t j = 0; j < count; ++j) h_list[j] = make_uint2(list[j], static_cast<uint32_t>(c->m));
             if (list && hipMemcpyAsync(d_list, h_list, count * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
@@ -1707,8 +1720,12 @@ int scrub_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, cons
 // behind them: the jobs and tables go up in one copy, the counts and fail
 // words come back in one.  Two host round trips: the verdicts, then the
 // counters together with the final verify's verdicts of the same stripes.
-int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint8_t* erased, int* status,
-                    uint32_t* corrected, hipStream_t s) {
+// shard_ptrs: pointer mode (rs_correct_columns_ptrs), the [stripes][n] shard
+// address table in device memory and v = StripeView::ptrs; the verifies and
+// the column kernel then run their pointer-mode forms, everything else is the
+// same.
+int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const uint8_t* erased,
+                    const uint64_t* shard_ptrs, int* status, uint32_t* corrected, hipStream_t s) {
     const size_t n = static_cast<size_t>(c->n);
     const size_t list_off = round_up(stripes * sizeof(uint32_t), 16);
     const size_t jobs_off = round_up(list_off + stripes * sizeof(uint2), 16);
@@ -1728,8 +1745,9 @@ int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, co
     // verdicts are at db afterwards.
     auto verify = [&](const uint32_t* list, size_t count) -> int {
         if (erased) {
-            const int rc = rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), &cp);
-            return rc != RS_OK ? rc : check_stripes(c, L, v, stripes, cp, reinterpret_cast<uint32_t*>(db), s);
+            const int rc = plan_view_checks(c, v, shard_ptrs, stripes, erased, list, count, &cp);
+            return rc != RS_OK ? rc
+                               : check_stripes(c, L, v, stripes, cp, shard_ptrs, reinterpret_cast<uint32_t*>(db), s);
         }
         uint2* h_list = reinterpret_cast<uint2*>(hb + list_off);
         uint2* d_list = reinterpret_cast<uint2*>(db + list_off);
@@ -1737,7 +1755,7 @@ int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, co
         if (list && hipMemcpyAsync(d_list, h_list, count * sizeof(uint2), hipMemcpyHostToDevice, s) != hipSuccess)
             return RS_EDEVICE;
         return launch_verify_stripes(c, v, stripes, list ? d_list : nullptr, list ? count : stripes,
-                                     reinterpret_cast<uint32_t*>(db), s);
+                                     reinterpret_cast<uint32_t*>(db), s, shard_ptrs);
     };
     int rc = verify(nullptr, 0);
     if (rc != RS_OK) return rc;
@@ -1786,6 +1804,7 @@ int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, co
     a.k = static_cast<uint32_t>(c->k);
     a.n = static_cast<uint32_t>(c->n);
     a.njobs = static_cast<uint32_t>(nd);
+    a.shard_ptrs = shard_ptrs;
     if (!rsmi::plan_column_correct(&a)) return RS_EINVAL;
 
     const size_t tb = rsmi::column_table_bytes(c->n);
@@ -3136,6 +3155,8 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 7) return rsmi::update_degraded_variant_name(c->m);
     if (which == 8) return rsmi::column_variant_name(c->m);
     if (which == 9) return rsmi::combine_lens_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
+    if (which == 10) return rsmi::check_ptrs_variant_name(c->k);
+    if (which == 11) return rsmi::column_ptrs_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3376,7 +3397,7 @@ int rs_verify_degraded(rs_ctx* c, const void* data, size_t dss, const void* pari
     }
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
-    return check_stripes(c, *sc.L, v, stripes, plan, first_bad, static_cast<hipStream_t>(stream));
+    return check_stripes(c, *sc.L, v, stripes, plan, nullptr, first_bad, static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
@@ -3428,7 +3449,7 @@ int rs_correct_columns(rs_ctx* c, void* data, size_t dss, void* parity, size_t p
     if (c->m == 0) return RS_OK;  // no parity: every stripe is a codeword
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
-    return correct_columns(c, *sc.L, v, stripes, degraded ? erased : nullptr, status, corrected,
+    return correct_columns(c, *sc.L, v, stripes, degraded ? erased : nullptr, nullptr, status, corrected,
                            static_cast<hipStream_t>(stream));
 }
 
@@ -3552,6 +3573,60 @@ int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_
     if (sc.error() != RS_OK) return sc.error();
     return reconstruct(c, *sc.L, StripeView::ptrs(round_up(len, 16), len), stripes, erased, shard_ptrs,
                        static_cast<hipStream_t>(stream));
+}
+
+int rs_verify_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
+                   uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+    if (!first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    if (round_up(len, 16) / 16 >= (size_t(1) << 28)) return RS_EINVAL;  // 32-bit column offsets
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    const StripeView v = StripeView::ptrs(round_up(len, 16), len);
+    rsmi::CheckPlan plan;
+    if (erased) {
+        const int rc = rsmi::plan_checks_ptrs(c->k, c->n, stripes, erased, nullptr, 0, &plan);
+        if (rc != RS_OK) return rc;
+    }
+    // No flag set: rs_verify_stripes' launch, without a lock or a lease.
+    if (!erased || plan.intact.size() == stripes) {
+        DeviceGuard g(c->device);
+        if (!g.ok) return RS_EDEVICE;
+        return launch_verify_stripes(c, v, stripes, nullptr, stripes, first_bad, static_cast<hipStream_t>(stream),
+                                     shard_ptrs);
+    }
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return check_stripes(c, *sc.L, v, stripes, plan, shard_ptrs, first_bad, static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_columns_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
+                            int* status, uint32_t* corrected, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+    if (round_up(len, 16) / 16 >= (size_t(1) << 28)) return RS_EINVAL;  // 32-bit column offsets
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the job list
+    if (c->m > rsmi::kColumnMaxSyn) return RS_EINVAL;  // the kernel keeps at most 16 syndromes per column
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    // The erasure counts are checked before anything is written or launched.
+    const size_t n = static_cast<size_t>(c->n);
+    bool degraded = false;
+    for (size_t i = 0; erased && i < stripes; ++i) {
+        int e = 0;
+        for (size_t id = 0; id < n; ++id) e += erased[i * n + id] != 0;
+        if (e > c->m) return RS_ENOT_ENOUGH;
+        degraded |= e > 0;
+    }
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (corrected) std::fill(corrected, corrected + stripes * n, 0u);
+    if (c->m == 0) return RS_OK;  // no parity: every stripe is a codeword
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return correct_columns(c, *sc.L, StripeView::ptrs(round_up(len, 16), len), stripes, degraded ? erased : nullptr,
+                           shard_ptrs, status, corrected, static_cast<hipStream_t>(stream));
 }
 
 int rs_encode(rs_ctx* c, const uint8_t* input, size_t len, uint8_t* parity) {

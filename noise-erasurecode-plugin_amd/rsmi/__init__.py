@@ -38,6 +38,7 @@ EXPORTS = (
     "rs_new", "rs_new_on_device", "rs_free", "rs_k", "rs_n", "rs_device",
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
+    "rs_verify_ptrs", "rs_correct_columns_ptrs",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
     "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
@@ -162,6 +163,8 @@ def _lib() -> ctypes.CDLL:
             "rs_encode_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp]),
             "rs_reconstruct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_reconstruct_ptrs": (i32, [vp, vp, sz, sz, vp, vp]),
+            "rs_verify_ptrs": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+            "rs_correct_columns_ptrs": (i32, [vp, vp, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
             "rs_update_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
@@ -690,6 +693,44 @@ class FEC:
         _check(_lib().rs_reconstruct_ptrs(self._h, shard_ptrs_dev, shard_len, stripes,
                                           ctypes.cast(buf, ctypes.c_void_p), stream or None),
                "rs_reconstruct_ptrs")
+
+    def verify_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, first_bad_ptr: int,
+                    erased: Optional[bytes] = None, stream: int = 0) -> None:
+        """rs_verify_ptrs: verify_degraded (verify_stripes without flags) for
+        shards at the device addresses in the device array
+        shard_ptrs_dev[s * n + i], as reconstruct_ptrs.  Entries of erased
+        shards are never dereferenced.  Enqueued on stream."""
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_verify_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
+                                     ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None, stream or None),
+               "rs_verify_ptrs")
+
+    def correct_columns_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int,
+                             erased: Optional[bytes] = None, stream: int = 0):
+        """rs_correct_columns_ptrs: correct_columns for shards at the device
+        addresses in shard_ptrs_dev[s * n + i].  Returns (status, corrected):
+        the status list as correct_columns, corrected a uint32 ndarray of
+        stripes * n counts.  The ranges of the present shards must not
+        overlap.  Raises only for argument, device or memory errors and for
+        more than m erasures."""
+        import numpy as np
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        st = (ctypes.c_int * max(stripes, 1))()
+        cnt = np.zeros(max(stripes * self.n, 1), dtype=np.uint32)
+        rc = _lib().rs_correct_columns_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
+                                            ctypes.cast(buf, ctypes.c_void_p), st,
+                                            ctypes.c_void_p(cnt.ctypes.data), stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_columns_ptrs")
+        return [st[s] for s in range(stripes)], cnt[:stripes * self.n]
 
     def pattern_count(self) -> int:
         return _lib().rs_pattern_count(self._h)

@@ -384,21 +384,50 @@ def gather_survivors(held, plan: ExchangePlan, bufs: GatherBuffers, group=None, 
     return bufs
 
 
+class InconsistentSurvivors(RuntimeError):
+    """reconstruct_owned(verify=True): the gathered shards of some owned
+    stripes do not lie on one codeword.  `stripes` holds (index among the
+    owned stripes, first bad byte offset) pairs."""
+
+    def __init__(self, stripes):
+        super().__init__(f"{len(stripes)} owned stripes failed rs_verify_ptrs before the reconstruct, first: {stripes[:4]}")
+        self.stripes = stripes
+
+
 def reconstruct_owned(fec, plan: ExchangePlan, table_dev, erased_owned: np.ndarray, shard_bytes: int,
-                      stream: int = 0, chunk: Optional[int] = None) -> None:
+                      stream: int = 0, chunk: Optional[int] = None, verify: bool = False) -> None:
     """Regenerates the erased shards of the owned stripes (all, or one
     chunk's) into the output buffer the shard table (a device int64 tensor
-    from shard_table) points at."""
+    from shard_table) points at.
+
+    verify: rs_verify_ptrs runs over the same table first, with the stripes'
+    erasure flags plus a flag for every shard the table does not hold (UNUSED:
+    present, but never gathered), and InconsistentSurvivors is raised before
+    anything is regenerated if a stripe is not clean.  It waits for the
+    verdicts, so the step loses its overlap.  A stripe needs more than k
+    shards in the table to be checked at all: one whose table holds exactly
+    the k survivors of Rebuild is clean by definition."""
     n = plan.kind.shape[1]
     lo, hi = (0, len(plan.owned)) if chunk is None else (plan.chunks[chunk].lo, plan.chunks[chunk].hi)
     if hi <= lo:
         return
     er = np.ascontiguousarray(np.asarray(erased_owned)[lo:hi], dtype=np.uint8)
+    if verify:
+        import torch
+        absent = np.ascontiguousarray((er != 0) | (plan.kind[lo:hi] == UNUSED), dtype=np.uint8)
+        first_bad = torch.empty(hi - lo, dtype=torch.int32, device=table_dev.device)
+        fec.verify_ptrs(table_dev.data_ptr() + lo * n * 8, shard_bytes, hi - lo, first_bad.data_ptr(),
+                        erased=absent.tobytes(), stream=stream)
+        fec.sync(stream)
+        fb = first_bad.cpu().numpy().view(np.uint32)
+        bad = np.flatnonzero(fb != 0xFFFFFFFF)
+        if bad.size:
+            raise InconsistentSurvivors([(int(lo + j), int(fb[j])) for j in bad])
     fec.reconstruct_ptrs(table_dev.data_ptr() + lo * n * 8, shard_bytes, hi - lo, er.tobytes(), stream)
 
 
 def run_step(fec, held, plan: ExchangePlan, bufs: GatherBuffers, table_dev, erased_owned: np.ndarray,
-             shard_bytes: int, compute_stream, comm_stream=None, group=None):
+             shard_bytes: int, compute_stream, comm_stream=None, group=None, verify: bool = False):
     """One pipelined step: chunk c's exchange on comm_stream, its
     reconstruct on compute_stream after the exchange's event.  Before an
     exchange lands in receive slot s, comm_stream waits for bufs.slot_free[s]
@@ -408,15 +437,20 @@ def run_step(fec, held, plan: ExchangePlan, bufs: GatherBuffers, table_dev, eras
     step i's last reconstructs still read).  Without a comm stream the
     chunks run one after the other on the current stream.
 
+    verify: every chunk's reconstruct verifies its gathered shards first
+    (reconstruct_owned).
+
     Returns (start, end): compute-stream events recorded before the step's
     first reconstruct is queued and after its last one (None, None without a
     comm stream)."""
     import torch
     slots = bufs.slots
+    opts = {"verify": True} if verify else {}  # the default call stays as it was
     if comm_stream is None:
         for c in range(len(plan.chunks)):
             gather_survivors(held, plan, bufs, group, c)
-            reconstruct_owned(fec, plan, table_dev, erased_owned, shard_bytes, compute_stream.cuda_stream, c)
+            reconstruct_owned(fec, plan, table_dev, erased_owned, shard_bytes, compute_stream.cuda_stream, c,
+                              **opts)
         return None, None
     start = torch.cuda.Event(enable_timing=True)
     start.record(compute_stream)
@@ -429,7 +463,8 @@ def run_step(fec, held, plan: ExchangePlan, bufs: GatherBuffers, table_dev, eras
             got = torch.cuda.Event()
             got.record(comm_stream)
         compute_stream.wait_event(got)
-        reconstruct_owned(fec, plan, table_dev, erased_owned, shard_bytes, compute_stream.cuda_stream, c)
+        reconstruct_owned(fec, plan, table_dev, erased_owned, shard_bytes, compute_stream.cuda_stream, c,
+                          **opts)
         ev = torch.cuda.Event()
         ev.record(compute_stream)
         bufs.slot_free[slot] = ev
