@@ -85,7 +85,10 @@ const char *rs_strerror(int status);
  * mixed lengths, e.g. "combine_lens_MG4_B256"; which = 10 and 11: the
  * pointer-mode twins of which = 5 and 8 that serve rs_verify_ptrs and
  * rs_correct_columns_ptrs, e.g. "check_K10_MG4_B256_ptrs" and
- * "columns_MG4_B256_ptrs". */
+ * "columns_MG4_B256_ptrs"; which = 12 and 13: the repair kernel of
+ * rs_reconstruct_checked and its pointer-mode twin of
+ * rs_reconstruct_checked_ptrs, e.g. "repair_K10_MG4_B256" and
+ * "repair_K10_MG4_B256_ptrs". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -289,6 +292,47 @@ int rs_correct_degraded(rs_ctx *ctx, void *data, size_t data_stripe_stride, void
                         size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
                         size_t stripes, const uint8_t *erased, int *status,
                         uint8_t *rewritten, void *stream);
+
+/* Checked repair: rs_reconstruct_stripes that also says whether the survivors
+ * it read could be trusted -- rs_verify_degraded and rs_reconstruct_stripes in
+ * one pass over the stripe (n * S bytes moved per degraded stripe instead of
+ * (2k + m) * S).  Layout, alignment, erased (HOST, stripes * n flags, not
+ * retained) and first_bad (DEVICE, uint32[stripes]) as for rs_verify_degraded.
+ * When stream has run:
+ *  1. the slot of every erased shard holds the round_up(shard_len, 16) bytes
+ *     rs_reconstruct_stripes would have written there, bit for bit, whether or
+ *     not the stripe's check passes;
+ *  2. first_bad[s] is what rs_verify_degraded would have written for the
+ *     stripes as they were before the call: the lowest byte offset below
+ *     shard_len at which the PRESENT shards of stripe s do not lie on one
+ *     codeword, or RS_VERIFY_CLEAN.  Bytes at or beyond shard_len are not
+ *     compared; a stripe with exactly m erasures has nothing to compare and is
+ *     clean; a stripe without erasures gets rs_verify_stripes' verdict;
+ *  3. nothing else is written: no present shard, no pad or pitch gap, no stride
+ *     gap.  Of a stripe's present shards only Rebuild's k survivors and the
+ *     m - e others that are compared are read, and nothing is ever read from
+ *     the slot of an erased shard.
+ * A stripe whose first_bad is not RS_VERIFY_CLEAN has had its missing slots
+ * filled from survivors that cannot be trusted.  Keep that stripe's flags, run
+ * rs_correct_columns (or rs_correct_degraded) with them, then reconstruct
+ * again.
+ * Refused with nothing launched or written: RS_ENOT_ENOUGH when any stripe has
+ * more than m erasures; RS_EINVAL for a NULL ctx, NULL erased or first_bad, and
+ * for everything rs_verify_degraded refuses (stripes >= 2^32 and the column
+ * limit included).  stripes == 0 or shard_len == 0: RS_OK.  With m == 0 and no
+ * flag set every stripe is clean.  Enqueued on stream; returns when queued,
+ * like the two calls it fuses.  The stripes the repair kernel served count
+ * into RS_STAT_REPAIR_CHECKED; stripes without erasures go through the verify
+ * kernel and are not counted.  Two A/B knobs, both read at rs_new: a context
+ * created under RSMI_REPAIR_FUSED=0 queues the two existing launches on stream
+ * instead, with the same contract (its stripes count into
+ * RS_STAT_CHECK_STRIPES and RS_STAT_REC_STRIPES_* as theirs do);
+ * RSMI_XCD_REPAIR_REGION=N sets the repair kernel's blocks per XCD region (0:
+ * natural order, the default for m <= 4; otherwise a stripe per region), as
+ * RSMI_XCD_REC_REGION does for the reconstruct. */
+int rs_reconstruct_checked(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                           size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len,
+                           size_t stripes, const uint8_t *erased, uint32_t *first_bad, void *stream);
 
 /* Column scrub: infectious Correct, stripe-batched -- every byte column of
  * every stripe decoded on its own (Berlekamp-Welch's result, column by column).
@@ -609,9 +653,20 @@ int rs_reconstruct_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_le
  * again), synchronous, RS_EINVAL for m > 16.  Bytes at offsets >= shard_len,
  * clean stripes and the table are never written.  The caller guarantees
  * (not checked: the table lives on the device) that the ranges of the
- * present shards named by the table do not overlap each other. */
+ * present shards named by the table do not overlap each other.
+ *
+ * rs_reconstruct_checked_ptrs is rs_reconstruct_checked on that placement:
+ * the slots of rs_reconstruct_ptrs, the verdicts of rs_verify_ptrs, points 1
+ * to 3 and the recipe as there, and the table itself is never written.
+ * erased must not be NULL.  Unlike rs_verify_ptrs, the call loads the table
+ * entries of ERASED shards: they are the destinations, so they have to be
+ * valid (16-byte aligned, round_up(shard_len, 16) writable bytes) and disjoint
+ * from each other and from every present shard of the call.  Counts into
+ * RS_STAT_REPAIR_CHECKED. */
 int rs_verify_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
                    const uint8_t *erased, uint32_t *first_bad, void *stream);
+int rs_reconstruct_checked_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
+                                const uint8_t *erased, uint32_t *first_bad, void *stream);
 int rs_correct_columns_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
                             const uint8_t *erased, int *status, uint32_t *corrected, void *stream);
 
@@ -651,6 +706,7 @@ enum {
     RS_STAT_COLUMN_BYTES = 23,     /* bytes rs_correct_columns corrected                */
     RS_STAT_BATCH_LENS_PASSES = 24, /* GPU passes of rs_encode_batch_lens / rs_decode_batch_lens (one per staging group) */
     RS_STAT_COMBINE_LENS_LAUNCHES = 25, /* rs_combine_lens calls served by the per-job-length kernel (not by rs_combine's) */
+    RS_STAT_REPAIR_CHECKED = 26,   /* stripes repaired and checked by the repair kernel (rs_reconstruct_checked*) */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -762,7 +818,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *  - the device-resident calls (rs_encode_stripes, rs_reconstruct_stripes,
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
  *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
- *    rs_verify_ptrs, rs_correct_columns_ptrs,
+ *    rs_verify_ptrs, rs_correct_columns_ptrs, rs_reconstruct_checked, rs_reconstruct_checked_ptrs,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

@@ -16,8 +16,9 @@ void clear(CheckPlan* plan) {
 }
 
 // The planner of both placements: dst_of(stripe, id) is what an entry carries
-// for the stored shard `id` of `stripe`.
-template <class DstOf>
+// for the shard `id` of `stripe`.  Repair (plan_repairs): saturated stripes
+// get a job too and every id of X' an entry, its pad saying stored or compared.
+template <bool Repair, class DstOf>
 int plan_impl(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count, DstOf dst_of,
               CheckPlan* plan) {
     if (!plan) return RS_EINVAL;
@@ -46,14 +47,15 @@ int plan_impl(int k, int n, size_t stripes, const uint8_t* erased, const uint32_
         }
         if (e == m) {
             ++plan->saturated;
-            continue;
+            if (!Repair) continue;
         }
         // Rebuild takes every present data share and fills up to k with the
         // highest-numbered present parity: the m - e present parity shards it
         // leaves out, the lowest-numbered ones, are U (always parity shards).
         const int j = m - e;
-        plan->jobs.push_back(ReadJob{stripe, static_cast<uint32_t>(plan->entries.size()), static_cast<uint32_t>(j)});
-        plan->max_j = std::max(plan->max_j, static_cast<uint32_t>(j));
+        const uint32_t nent = static_cast<uint32_t>(Repair ? m : j);
+        plan->jobs.push_back(ReadJob{stripe, static_cast<uint32_t>(plan->entries.size()), nent});
+        plan->max_j = std::max(plan->max_j, nent);
         const size_t f0 = plan->flags.size();
         plan->flags.resize(f0 + static_cast<size_t>(n));
         uint8_t* xf = &plan->flags[f0];
@@ -70,7 +72,10 @@ int plan_impl(int k, int n, size_t stripes, const uint8_t* erased, const uint32_
         uint32_t rank = 0;
         for (int id = 0; id < n; ++id) {
             if (!xf[id]) continue;
-            if (!fl[id]) plan->entries.push_back(ReadEntry{dst_of(stripe, id), rank, 0u});
+            if (Repair)
+                plan->entries.push_back(ReadEntry{dst_of(stripe, id), rank, fl[id] ? kRepairStore : kRepairCompare});
+            else if (!fl[id])
+                plan->entries.push_back(ReadEntry{dst_of(stripe, id), rank, 0u});
             ++rank;
         }
     }
@@ -80,18 +85,36 @@ int plan_impl(int k, int n, size_t stripes, const uint8_t* erased, const uint32_
 
 int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
                 const CheckLayout& lay, CheckPlan* plan) {
-    return plan_impl(k, n, stripes, erased, list, count,
-                     [&](uint32_t stripe, int id) {
-                         return lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
-                                static_cast<uint64_t>(id - k) * lay.pitch;
-                     },
-                     plan);
+    return plan_impl<false>(k, n, stripes, erased, list, count,
+                            [&](uint32_t stripe, int id) {
+                                return lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
+                                       static_cast<uint64_t>(id - k) * lay.pitch;
+                            },
+                            plan);
 }
 
 int plan_checks_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
                      CheckPlan* plan) {
-    return plan_impl(k, n, stripes, erased, list, count,
-                     [](uint32_t, int id) { return static_cast<uint64_t>(id); }, plan);
+    return plan_impl<false>(k, n, stripes, erased, list, count,
+                            [](uint32_t, int id) { return static_cast<uint64_t>(id); }, plan);
+}
+
+int plan_repairs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                 const CheckLayout& lay, CheckPlan* plan) {
+    return plan_impl<true>(k, n, stripes, erased, list, count,
+                           [&](uint32_t stripe, int id) {
+                               return id < k ? lay.data + static_cast<uint64_t>(stripe) * lay.data_ss +
+                                                   static_cast<uint64_t>(id) * lay.pitch
+                                             : lay.parity + static_cast<uint64_t>(stripe) * lay.parity_ss +
+                                                   static_cast<uint64_t>(id - k) * lay.pitch;
+                           },
+                           plan);
+}
+
+int plan_repairs_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                      CheckPlan* plan) {
+    return plan_impl<true>(k, n, stripes, erased, list, count,
+                           [](uint32_t, int id) { return static_cast<uint64_t>(id); }, plan);
 }
 
 }  // namespace rsmi

@@ -57,4 +57,24 @@ int plan_checks(int k, int n, size_t stripes, const uint8_t* erased, const uint3
 int plan_checks_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
                      CheckPlan* plan);
 
+// The plan of rs_reconstruct_checked / rs_reconstruct_checked_ptrs (the repair
+// kernel): one launch regenerates the erased shards X of a stripe and checks
+// its present shards U = present \ C, both from the same k survivors C, so
+// every row of the pattern of X' = X + U is wanted.  The splits, survivors,
+// flags and refusals are plan_checks', except that
+//   - every stripe with 1 <= e <= m becomes a job, the saturated ones (still
+//     counted in `saturated`) included: they have shards to regenerate;
+//   - a job has exactly m entries, the ids of X' in increasing order, entry t
+//     with row t; dst is the address of the shard's slot (plan_repairs_ptrs:
+//     the shard's id), data shards included;
+//   - an entry's pad says what becomes of its row: kRepairStore (id in X, the
+//     slot is written and never read) or kRepairCompare (id in U, the slot is
+//     read and never written);
+//   - max_j is m whenever there is a job.
+constexpr uint32_t kRepairCompare = 0u, kRepairStore = 1u;
+int plan_repairs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                 const CheckLayout& lay, CheckPlan* plan);
+int plan_repairs_ptrs(int k, int n, size_t stripes, const uint8_t* erased, const uint32_t* list, size_t count,
+                      CheckPlan* plan);
+
 }  // namespace rsmi

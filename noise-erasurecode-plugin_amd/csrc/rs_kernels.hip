@@ -1334,6 +1334,231 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
     }
 }
 
+// Checked repair (rs_kernels.hpp launch_repair): rs_check_kernel and
+// rs_read_kernel in one pass over the survivors, a sibling of the check kernel
+// with a body of its own.  A job's entries are all m ids of X' (plan_repairs),
+// entry t with row t, and entries[..].pad says what becomes of the row:
+//   compare  the id is a present shard outside the survivors: its stored
+//            column is preloaded into the accumulator and feeds the first_bad
+//            reduction, exactly as in the check kernel; nothing is stored;
+//   store    the id is erased: the accumulator starts at zero, no load from
+//            the slot is ever issued, and the row ends in one 16-byte store
+//            per column (tail lanes, which re-read the last column, do not
+//            store).
+// The store bits of the group's rows are one wave-uniform mask, so every branch
+// on them is scalar.  The survivors are never among the entries: a block's
+// stores cannot alias anything it or another block reads.
+// LDS: [k][20] table dwords | k survivor pointers.
+//
+// PTRS (compile-time twin, launch_repair_ptrs): as the check kernel's, and the
+// table entries of erased shards are loaded too: they are the destinations.
+template <int K, int MG, int BT, bool NT, bool PTRS = false>
+__global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, CheckPtrArgs, ReadArgs> a,
+                                                       uint32_t* first_bad, uint32_t shard_len) {
+    extern __shared__ uint4 lds4[];
+    static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
+    constexpr bool kRegPtrs = K > 0 && K <= 16;           // survivor bases kept in SGPRs
+    constexpr int JB = (K == 0) ? 8 : (K <= 16 ? K : 8);  // survivor loads in flight
+    const int k = K ? K : static_cast<int>(a.k);
+    uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
+    uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * kStepWords);
+
+    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    b /= a.groups;
+    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
+    const uint64_t ji = b / a.chunks;
+    const ReadJob job = a.jobs[ji];
+    // Stripe indices of a repair fit 32 bits (plan_repairs).
+    const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe)));
+    const int j = __builtin_amdgcn_readfirstlane(job.j);
+    const int row0 = static_cast<int>(grp) * MG;
+    if (row0 >= j) return;  // whole block: uniform
+    const int eg = min(MG, j - row0);
+    const ReadEntry* ent = a.entries + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(job.first)) + row0;
+    const uint32_t pat = __builtin_amdgcn_readfirstlane(a.pats[ji]);
+
+    // This lane's coefficient byte for the table build is requested first, so
+    // waiting for it later does not wait for the survivor loads behind it.
+    // Entry t of a job has row t (plan_repairs): the rows of the group are
+    // row0 .. row0 + eg - 1, and the request does not wait for the entry table.
+    const uint8_t* coef = a.coef + (static_cast<size_t>(pat) * a.m + row0) * k;
+    constexpr bool one_coef = (K > 0 && K * MG <= BT);
+    uint32_t cbyte = 0u;
+    if constexpr (one_coef) {
+        const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+        if (static_cast<int>(threadIdx.x) < k * MG && t < eg) cbyte = coef[t * k + c];
+    }
+
+    const uint32_t* srcid = a.src + static_cast<size_t>(pat) * k;
+    uint8_t* sp[kRegPtrs ? K : 1];
+    const uint64_t* tp = nullptr;  // pointer mode: the stripe's row of the shard table
+    if constexpr (PTRS) {
+        tp = a.shard_ptrs + s * (a.k + a.m);
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
+#pragma unroll
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+            for (int c = 0; c < K; ++c) sp[c] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[ids[c]]));
+        } else {
+            for (int i = threadIdx.x; i < k; i += BT) sptr[i] = reinterpret_cast<uint8_t*>(tp[srcid[i]]);
+        }
+    } else {
+        uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
+        uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
+#pragma unroll
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+                sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
+                                                         : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+        } else {
+            for (int i = threadIdx.x; i < k; i += BT) {
+                const uint32_t id = srcid[i];
+                sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                                   : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+            }
+        }
+    }
+    const uint32_t last = a.ncols16 - 1;
+    // Survivor loads of the block's first iteration go out before the table
+    // build, as in matmul_block.
+    uint4 xpre[kRegPtrs ? K : 1];
+    const uint32_t cstride = a.chunks * BT;
+    const uint32_t col0 = chunk * BT + threadIdx.x;
+    const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
+    if constexpr (kRegPtrs) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + off0);
+    }
+    // Slots of the group's rows and their store bits (bit t: row t is stored);
+    // rows past eg have neither.
+    uint8_t* dp[MG];
+    uint32_t st = 0u;
+#pragma unroll
+    for (int t = 0; t < MG; ++t)
+        if (t < eg) st |= (__builtin_amdgcn_readfirstlane(ent[t].pad) & 1u) << t;
+    if constexpr (PTRS) {
+        // The entries carry shard ids: all of them first, then their addresses.
+        uint32_t oid[MG];
+#pragma unroll
+        for (int t = 0; t < MG; ++t)
+            oid[t] = t < eg ? __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(ent[t].dst)) : 0u;
+#pragma unroll
+        for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(tp[oid[t]])) : nullptr;
+    } else {
+#pragma unroll
+        for (int t = 0; t < MG; ++t) dp[t] = t < eg ? uniform_ptr(reinterpret_cast<uint8_t*>(ent[t].dst)) : nullptr;
+    }
+    const uint32_t cmp = ~st & ((1u << eg) - 1u);  // bit t: row t is compared
+    // The accumulators of compare rows start as the stored columns, loaded next
+    // to the survivors so they ride the same latency; those of store rows and
+    // of rows past eg start at zero, and nothing is read from their slots.
+    uint32_t acc[kRowsPerStep][4];
+    auto load_stored = [&](uint32_t at) {
+#pragma unroll
+        for (int r = 0; r < kRowsPerStep; ++r) {
+            uint4 p = make_uint4(0u, 0u, 0u, 0u);
+            if (cmp & (1u << r)) p = gload16<NT>(dp[r] + at);
+            acc[r][0] = p.x;
+            acc[r][1] = p.y;
+            acc[r][2] = p.z;
+            acc[r][3] = p.w;
+        }
+    };
+    load_stored(off0);
+    // Split tables of the group's rows: survivor c's sub-step holds 4 x 5 dwords.
+    if constexpr (one_coef) {
+        if (static_cast<int>(threadIdx.x) < k * MG) {
+            const int c = threadIdx.x / MG, t = threadIdx.x - c * MG;
+            build_tables(cbyte, &tw[c * kStepWords + t * 5]);
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < k * MG; idx += BT) {
+            const int c = idx / MG, t = idx - c * MG;
+            const uint32_t cf = (t < eg) ? coef[t * k + c] : 0u;
+            build_tables(cf, &tw[c * kStepWords + t * 5]);
+        }
+    }
+    __syncthreads();
+
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint32_t colbase = chunk * BT + it * cstride;
+        if (colbase >= a.ncols16) break;
+        RS_MEM_FENCE();
+        const uint32_t col = colbase + threadIdx.x;
+        const bool ok = col <= last;  // tail lanes re-read the last column (always in bounds): no report, no store
+        const uint32_t off = (ok ? col : last) * 16u;
+
+        for (int jb = 0; jb < k; jb += JB) {
+            uint4 xb[kRegPtrs ? 1 : JB];
+            uint4* x = kRegPtrs ? xpre : xb;
+            if constexpr (!kRegPtrs) {
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (K == 0 && jb + q >= k) break;
+                    x[q] = gload16<NT>(uniform_ptr(sptr[jb + q]) + off);
+                }
+            }
+            uint32_t TA[kStepWords], TB[kStepWords];
+            load_step(lds4 + static_cast<size_t>(jb) * (kStepWords / 4), TA);
+#pragma unroll
+            for (int q = 0; q < JB; ++q) {
+                if (K == 0 && jb + q >= k) break;
+                const bool more = q + 1 < JB && (K != 0 || jb + q + 1 < k);
+                if (more) load_step(lds4 + static_cast<size_t>(jb + q + 1) * (kStepWords / 4), TB);
+                mac_step_rows(acc, x[q], TA, eg);
+                step_fence(acc);
+#pragma unroll
+                for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
+            }
+        }
+        const bool again = it + 1 < a.iters && colbase + cstride < a.ncols16;
+        const uint32_t ncol = colbase + cstride + threadIdx.x;
+        const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
+        if constexpr (kRegPtrs) {
+            // Software pipelining: the next iteration's survivor loads go out
+            // before this iteration's stores and compare.
+            if (again) {
+#pragma unroll
+                for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + noff);
+            }
+        }
+        // Store rows: the regenerated column, once.  Compare rows: the bytes at
+        // which the stored column differs from the recomputed one; tail lanes
+        // and bytes past shard_len do not count.
+        uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < kRowsPerStep; ++r) {
+            if (st & (1u << r)) {
+                if (ok) gstore16<NT>(dp[r] + off, make_uint4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]));
+            } else {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) d[w] |= acc[r][w];
+            }
+        }
+        if (cmp) {  // uniform: a group of store rows has nothing to report
+            const uint32_t nb = ok ? min(16u, shard_len - col * 16u) : 0u;  // bytes of this column below shard_len
+            uint32_t byte = 16u;
+#pragma unroll
+            for (int w = 3; w >= 0; --w) {
+                const uint32_t nbw = nb > 4u * w ? min(4u, nb - 4u * w) : 0u;
+                const uint32_t dw = d[w] & (nbw >= 4u ? ~0u : (1u << (8u * nbw)) - 1u);
+                if (dw) byte = 4u * w + (static_cast<uint32_t>(__builtin_ctz(dw)) >> 3);
+            }
+            // Lanes are in column order: the first mismatching lane holds the
+            // wave's lowest offset.
+            const bool bad = byte < 16u;
+            const uint64_t bal = __ballot(bad);
+            if (bad && (bal & ((1ull << __lane_id()) - 1ull)) == 0) atomicMin(&first_bad[s], col * 16u + byte);
+        }
+        if (again) load_stored(noff);
+    }
+}
+
 template <int K, int MG, int BT, bool NT>
 __global__ __launch_bounds__(BT) void rs_matmul_kernel(MatArgs a) {
     extern __shared__ uint4 lds4[];
@@ -1633,6 +1858,26 @@ const CheckVariant& pick_check(int k) {
     return kCheck[sizeof(kCheck) / sizeof(kCheck[0]) - 1];  // runtime k
 }
 
+// Repair variants: the check kernel's instances, one sibling each.
+struct RepairVariant {
+    int K;
+    const char* name;
+    void (*fn)(ReadArgs, uint32_t*, uint32_t);
+    const char* ptrs_name;  // the pointer-mode twin
+    void (*ptrs_fn)(CheckPtrArgs, uint32_t*, uint32_t);
+};
+#define RS_REPAIR(K)                                                                                      \
+    {K, "repair_K" #K "_MG4_B256", rs_repair_kernel<K, 4, kBlock, true>, "repair_K" #K "_MG4_B256_ptrs", \
+     rs_repair_kernel<K, 4, kBlock, true, true>}
+const RepairVariant kRepair[] = {RS_REPAIR(10), RS_REPAIR(4), RS_REPAIR(8), RS_REPAIR(64), RS_REPAIR(0)};
+#undef RS_REPAIR
+
+const RepairVariant& pick_repair(int k) {
+    for (const RepairVariant& v : kRepair)
+        if (v.K == k) return v;
+    return kRepair[sizeof(kRepair) / sizeof(kRepair[0]) - 1];  // runtime k
+}
+
 }  // namespace
 
 const char* update_variant_name(int m) { return pick_update(m, 0).name; }
@@ -1658,6 +1903,38 @@ hipError_t launch_check_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint
     if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
     if (!shard_ptrs) return hipErrorInvalidValue;
     const CheckVariant& v = pick_check(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    CheckPtrArgs pa{};
+    static_cast<ReadArgs&>(pa) = a;
+    pa.shard_ptrs = shard_ptrs;
+    hipLaunchKernelGGL(v.ptrs_fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, pa, first_bad,
+                       shard_len);
+    return hipGetLastError();
+}
+
+const char* repair_variant_name(int k) { return pick_repair(k).name; }
+
+const char* repair_ptrs_variant_name(int k) { return pick_repair(k).ptrs_name; }
+
+hipError_t launch_repair(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    const RepairVariant& v = pick_repair(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    // Unreachable behind plan_read, which refuses such a grid before the call
+    // has queued anything; kept as launch_check keeps it.
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a, first_bad, shard_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_repair_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad, uint32_t shard_len,
+                              hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    if (!shard_ptrs) return hipErrorInvalidValue;
+    const RepairVariant& v = pick_repair(static_cast<int>(a.k));
     const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;

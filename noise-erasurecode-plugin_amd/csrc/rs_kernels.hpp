@@ -290,6 +290,24 @@ hipError_t launch_check_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint
                              hipStream_t stream);  // a: planned
 const char* check_ptrs_variant_name(int k);  // "check_K10_MG4_B256_ptrs" etc.
 
+// Checked repair (rs_reconstruct_checked): the read and the check launch in
+// one, with the same arguments and plan (plan_read, max_j = m).  Job b's
+// entries are all m ids of the erasure set X' that pats[b] was built for
+// (plan_repairs), entry t with row t; entries[..].dst is the address of the
+// shard's slot and .pad says what happens to the row: kRepairStore -- the
+// shard is erased, the regenerated row is stored there and the slot is never
+// read -- or kRepairCompare -- the shard is present, the row is compared with
+// it as by launch_check, and the slot is never written.  (k + j) * S bytes
+// read and e * S written per job, j = m - e: n * S in all.
+hipError_t launch_repair(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream);  // a: planned
+const char* repair_variant_name(int k);  // "repair_K10_MG4_B256" etc.
+// Its twin for the pointer placement (rs_reconstruct_checked_ptrs), as
+// launch_check_ptrs: entries[..].dst holds shard ids (plan_repairs_ptrs), and
+// the table entries of the erased shards are loaded too, as destinations.
+hipError_t launch_repair_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad, uint32_t shard_len,
+                              hipStream_t stream);  // a: planned
+const char* repair_ptrs_variant_name(int k);  // "repair_K10_MG4_B256_ptrs" etc.
+
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard
 // id, for every shard of the stripe (a: strided layout, k, m).

@@ -372,11 +372,14 @@ struct rs_ctx {
     std::atomic<int64_t> update_stripes{0}, update_copy_commits{0};      // rs_update_stripes (rs_stat)
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
+    std::atomic<int64_t> repair_checked{0};                              // rs_reconstruct_checked: stripes of the repair kernel (rs_stat)
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
     std::atomic<int64_t> batch_lens_passes{0};                           // GPU passes of rs_encode_batch_lens / rs_decode_batch_lens
     std::atomic<int64_t> combine_lens_launches{0};                       // rs_combine_lens calls the per-job-length kernel served
     std::atomic<int64_t> update_degraded{0}, update_absorbed{0};         // rs_update_degraded (rs_stat)
     std::atomic<int64_t> column_stripes{0}, column_bytes{0};             // rs_correct_columns (rs_stat)
+    bool repair_fused = true;   // rs_reconstruct_checked: the repair kernel; false: the check and reconstruct launches (RSMI_REPAIR_FUSED=0)
+    uint32_t xcd_repair = 0;    // repair kernel: blocks per XCD region (0: natural order, ~0u: a stripe; RSMI_XCD_REPAIR_REGION)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
     hipEvent_t pat_ev = nullptr;
     hipStream_t build_stream = nullptr;  // pattern builds (flush_patterns), off every caller's stream
@@ -1455,6 +1458,82 @@ int plan_view_checks(const rs_ctx* c, const StripeView& v, const uint64_t* shard
                      const uint8_t* erased, const uint32_t* list, size_t count, rsmi::CheckPlan* plan) {
     return shard_ptrs ? rsmi::plan_checks_ptrs(c->k, c->n, stripes, erased, list, count, plan)
                       : rsmi::plan_checks(c->k, c->n, stripes, erased, list, count, check_layout(v), plan);
+}
+
+// ------------------------------------------------------- checked repair ----
+// Launches a planned checked repair on stream s, as launch_check_stripes: with
+// jobs, pat_mu is held and L.pid holds the built pattern of every job.  One
+// upload carries the intact stripes' list, the job and entry tables and the
+// jobs' pattern ids; then first_bad's preset and the verify kernel over the
+// intact stripes, then the repair kernel over the others: it regenerates their
+// erased shards and checks their present ones from one read of the survivors.
+int launch_repair_stripes(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, const rsmi::CheckPlan& plan,
+                          rsmi::ReadArgs a, const uint64_t* shard_ptrs, uint32_t* first_bad, hipStream_t s) {
+    const size_t nintact = plan.intact.size(), njobs = plan.jobs.size(), count = plan.entries.size();
+    const size_t job_off = round_up(nintact * sizeof(uint2), 16);
+    const size_t ent_off = job_off + njobs * sizeof(rsmi::ReadJob);
+    const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
+    const size_t bytes = pat_off + njobs * sizeof(uint32_t);
+    Tables t;
+    const int up = upload_tables(c, L, njobs, bytes, s, &t, [&](uint8_t* hb) {
+        uint2* desc = reinterpret_cast<uint2*>(hb);
+        for (size_t i = 0; i < nintact; ++i) desc[i] = make_uint2(plan.intact[i], static_cast<uint32_t>(c->m));
+        std::memcpy(hb + job_off, plan.jobs.data(), njobs * sizeof(rsmi::ReadJob));
+        std::memcpy(hb + ent_off, plan.entries.data(), count * sizeof(rsmi::ReadEntry));
+        std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+    });
+    if (up != RS_OK) return up;
+    int rc = launch_verify_stripes(c, v, stripes, reinterpret_cast<const uint2*>(t.dev), nintact, first_bad, s,
+                                   shard_ptrs);
+    if (rc == RS_OK) {
+        a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
+        a.src = static_cast<const uint32_t*>(c->d_psrc.p);
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev + job_off);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
+        rc = hip_status(shard_ptrs ? rsmi::launch_repair_ptrs(a, shard_ptrs, first_bad, static_cast<uint32_t>(v.len), s)
+                                   : rsmi::launch_repair(a, first_bad, static_cast<uint32_t>(v.len), s));
+    }
+    if (rc == RS_OK) c->repair_checked += static_cast<int64_t>(njobs);
+    return finish_launch(c, L, s, t.waited, rc);
+}
+
+// rs_reconstruct_checked / rs_reconstruct_checked_ptrs (shard_ptrs != nullptr)
+// behind their argument checks.  The plan is made before anything is written
+// or launched, so a stripe with more than m erasures refuses the whole call.
+// The repair kernel over plan_repairs'
+// jobs, their patterns (the erasure sets X') from the cache
+// rs_reconstruct_stripes fills; or, for a context created under
+// RSMI_REPAIR_FUSED=0 (rs_ctx::repair_fused), rs_verify_degraded's launches and then
+// rs_reconstruct_stripes' on the same stream and lease: the verify reads the
+// stripes as they were before the call, and no slot it reads is written by the
+// reconstruct behind it.
+int repair_checked(rs_ctx* c, const StripeView& v, const uint64_t* shard_ptrs, size_t stripes, const uint8_t* erased,
+                   uint32_t* first_bad, hipStream_t s) {
+    rsmi::CheckPlan plan;
+    const bool fused = c->repair_fused;
+    const int rc = fused ? (shard_ptrs ? rsmi::plan_repairs_ptrs(c->k, c->n, stripes, erased, nullptr, 0, &plan)
+                                       : rsmi::plan_repairs(c->k, c->n, stripes, erased, nullptr, 0, check_layout(v), &plan))
+                         : plan_view_checks(c, v, shard_ptrs, stripes, erased, nullptr, 0, &plan);
+    if (rc != RS_OK) return rc;
+    // No flag set: rs_verify_stripes' launch, without a lock or a lease.
+    if (plan.intact.size() == stripes) {
+        DeviceGuard g(c->device);
+        if (!g.ok) return RS_EDEVICE;
+        return launch_verify_stripes(c, v, stripes, nullptr, stripes, first_bad, s, shard_ptrs);
+    }
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    Lease& L = *sc.L;
+    if (!fused) {
+        const int vr = check_stripes(c, L, v, stripes, plan, shard_ptrs, first_bad, s);
+        return vr != RS_OK ? vr : reconstruct(c, L, v, stripes, erased, shard_ptrs, s);
+    }
+    rsmi::ReadArgs a = read_args(c, v, plan.jobs.size());
+    a.xcd = c->xcd_repair;
+    if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
+    return with_patterns(c, L, plan.flags.data(), plan.jobs.size(), s,
+                         [&] { return launch_repair_stripes(c, L, v, stripes, plan, a, shard_ptrs, first_bad, s); });
 }
 
 // ------------------------------------------------------ degraded update ----
@@ -2988,8 +3067,24 @@ int rs_new_on_device(int k, int n, int device, rs_ctx** out) {
         c->xcd_update = c->xcd ? ~0u : 0u;
         const char* uv = std::getenv("RSMI_XCD_UPD_REGION");  // A/B knob: blocks per XCD region
         if (uv) c->xcd_update = static_cast<uint32_t>(std::min(std::max(0, std::atoi(uv)), 1 << 20));
+        // The repair kernel: with one row group per stripe (m <= 4) the verify
+        // kernel's natural block order, with several the reconstruct's stripe
+        // per region, whose groups re-read the survivors from one L2.  Both
+        // choices are measured in DESIGN 4.19.
+        c->xcd_repair = c->xcd && c->m > 4 ? ~0u : 0u;
+        const char* pv = std::getenv("RSMI_XCD_REPAIR_REGION");  // A/B knob: blocks per XCD region
+        if (pv) c->xcd_repair = static_cast<uint32_t>(std::min(std::max(0, std::atoi(pv)), 1 << 20));
         const char* bv = std::getenv("RSMI_XCD_BS_STRIPES");  // A/B knob: stripes per region (bit-sliced)
         if (bv && c->xcd) c->xcd = static_cast<uint32_t>(std::min(std::max(1, std::atoi(bv)), 64));
+    }
+    {
+        // rs_reconstruct_checked: one repair kernel, for every code.  Also for
+        // those whose reconstruct runs the syndrome network: at config 5 the
+        // split-table repair kernel beats the check launch plus the syndrome
+        // reconstruct (DESIGN 4.19 has the table).  RSMI_REPAIR_FUSED=0 queues
+        // those two launches on the caller's stream instead (A/B runs, tests).
+        const char* rf = std::getenv("RSMI_REPAIR_FUSED");
+        c->repair_fused = rf ? std::atoi(rf) != 0 : true;
     }
     // Small reconstructs pass their descriptors in the kernel arguments
     // (launch_reconstruct); RSMI_NO_INLINE_DESC=1 uploads them always (A/B, tests).
@@ -3157,6 +3252,8 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 9) return rsmi::combine_lens_variant_name(c->k, c->m > 0 ? std::min(c->m, 4) : 1);
     if (which == 10) return rsmi::check_ptrs_variant_name(c->k);
     if (which == 11) return rsmi::column_ptrs_variant_name(c->m);
+    if (which == 12) return rsmi::repair_variant_name(c->k);
+    if (which == 13) return rsmi::repair_ptrs_variant_name(c->k);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3221,6 +3318,7 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_COLUMN_BYTES: return c->column_bytes.load();
         case RS_STAT_BATCH_LENS_PASSES: return c->batch_lens_passes.load();
         case RS_STAT_COMBINE_LENS_LAUNCHES: return c->combine_lens_launches.load();
+        case RS_STAT_REPAIR_CHECKED: return c->repair_checked.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3398,6 +3496,18 @@ int rs_verify_degraded(rs_ctx* c, const void* data, size_t dss, const void* pari
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
     return check_stripes(c, *sc.L, v, stripes, plan, nullptr, first_bad, static_cast<hipStream_t>(stream));
+}
+
+int rs_reconstruct_checked(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                           size_t stripes, const uint8_t* erased, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!erased || !first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    if (c->m > 0 && !check_stripes_args(c, v)) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (!route(c, c->m > 0 ? data : first_bad)) return RS_EINVAL;
+    return repair_checked(c, v, nullptr, stripes, erased, first_bad, static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_degraded(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
@@ -3600,6 +3710,19 @@ int rs_verify_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t str
     CallScope sc(c);
     if (sc.error() != RS_OK) return sc.error();
     return check_stripes(c, *sc.L, v, stripes, plan, shard_ptrs, first_bad, static_cast<hipStream_t>(stream));
+}
+
+int rs_reconstruct_checked_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes,
+                                const uint8_t* erased, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+    if (!erased || !first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    if (round_up(len, 16) / 16 >= (size_t(1) << 28)) return RS_EINVAL;  // 32-bit column offsets
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    return repair_checked(c, StripeView::ptrs(round_up(len, 16), len), shard_ptrs, stripes, erased, first_bad,
+                          static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_columns_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

@@ -39,6 +39,7 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_ptrs", "rs_correct_columns_ptrs",
+    "rs_reconstruct_checked", "rs_reconstruct_checked_ptrs",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
     "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
@@ -172,6 +173,8 @@ def _lib() -> ctypes.CDLL:
             "rs_read_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_verify_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
+            "rs_reconstruct_checked": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
+            "rs_reconstruct_checked_ptrs": (i32, [vp, vp, sz, sz, vp, vp, vp]),
             "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
             "rs_combine_lens": (i32, [vp, ctypes.POINTER(CombineJob), sz, ctypes.POINTER(sz), vp]),
@@ -559,6 +562,21 @@ class FEC:
                                          pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p),
                                          first_bad_ptr or None, stream or None), "rs_verify_degraded")
 
+    def reconstruct_checked(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                            pitch: int, shard_len: int, stripes: int, erased: bytes, first_bad_ptr: int,
+                            stream: int = 0) -> None:
+        """rs_reconstruct_checked: reconstruct_stripes and verify_degraded in
+        one pass (erased: stripes * n flags).  The erased slots are filled in
+        and first_bad_ptr[s] receives verify_degraded's verdict on the stripes
+        as they were before the call: a stripe that is not RS_VERIFY_CLEAN was
+        repaired from survivors that cannot be trusted.  Enqueued on stream."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_reconstruct_checked(self._h, data_ptr, data_stride, parity_ptr, parity_stride,
+                                             pitch, shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p),
+                                             first_bad_ptr or None, stream or None), "rs_reconstruct_checked")
+
     def correct_degraded(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
                          pitch: int, shard_len: int, stripes: int, erased: bytes, stream: int = 0):
         """rs_correct_degraded (scrub with missing shards): (status,
@@ -709,6 +727,19 @@ class FEC:
                                      ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None, stream or None),
                "rs_verify_ptrs")
 
+    def reconstruct_checked_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
+                                 first_bad_ptr: int, stream: int = 0) -> None:
+        """rs_reconstruct_checked_ptrs: reconstruct_checked for shards at the
+        device addresses in shard_ptrs_dev[s * n + i].  The entries of erased
+        shards are the destinations: valid, and disjoint from every present
+        shard.  Enqueued on stream."""
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_reconstruct_checked_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
+                                                  ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None,
+                                                  stream or None), "rs_reconstruct_checked_ptrs")
+
     def correct_columns_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int,
                              erased: Optional[bytes] = None, stream: int = 0):
         """rs_correct_columns_ptrs: correct_columns for shards at the device
@@ -741,7 +772,7 @@ class FEC:
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
      STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES, STAT_BATCH_LENS_PASSES,
-     STAT_COMBINE_LENS_LAUNCHES) = range(26)
+     STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED) = range(27)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
