@@ -88,7 +88,11 @@ const char *rs_strerror(int status);
  * "columns_MG4_B256_ptrs"; which = 12 and 13: the repair kernel of
  * rs_reconstruct_checked and its pointer-mode twin of
  * rs_reconstruct_checked_ptrs, e.g. "repair_K10_MG4_B256" and
- * "repair_K10_MG4_B256_ptrs". */
+ * "repair_K10_MG4_B256_ptrs"; which = 14, 15 and 16: the per-stripe-length
+ * twins of which = 2, 10 and 13 that serve rs_verify_ptrs_lens and
+ * rs_reconstruct_checked_ptrs_lens calls of mixed lengths, e.g.
+ * "verify_K10_MG4_B256_lens", "check_K10_MG4_B256_ptrs_lens" and
+ * "repair_K10_MG4_B256_ptrs_lens". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -670,6 +674,56 @@ int rs_reconstruct_checked_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t 
 int rs_correct_columns_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
                             const uint8_t *erased, int *status, uint32_t *corrected, void *stream);
 
+/* rs_verify_ptrs and rs_reconstruct_checked_ptrs for stripes that each have a
+ * shard length of their own (a store of objects of different sizes, scrubbed
+ * or repaired in one call): shard_lens is a HOST array of `stripes` lengths
+ * and is not retained; everything else is as in the equal-length calls.
+ * Stripe s is treated exactly as the equal-length call would treat it if it
+ * were called on that stripe alone with shard_len = shard_lens[s]:
+ *  - first_bad[s] is the lowest byte offset below shard_lens[s] at which the
+ *    present shards of stripe s do not lie on one codeword, or
+ *    RS_VERIFY_CLEAN; bytes at or beyond shard_lens[s] are never compared; a
+ *    stripe with exactly m erasures is clean; erased == NULL (nothing missing)
+ *    is allowed for the verify call only;
+ *  - the repair call stores, in the slot of every erased shard of stripe s,
+ *    the round_up(shard_lens[s], 16) bytes rs_reconstruct_ptrs would write
+ *    there, whether or not the stripe's check passes, and writes nothing else:
+ *    no present shard, nothing past round_up(shard_lens[s], 16) of any slot,
+ *    never the table.  The verify call never loads the table entries of erased
+ *    shards; for the repair call they are the destinations, valid and disjoint
+ *    as for rs_reconstruct_checked_ptrs;
+ *  - at most round_up(shard_lens[s], 16) bytes of a shard of stripe s are
+ *    read, and a stripe moves the bytes of the equal-length call at its own
+ *    length (stripes without erasures go through the verify kernel whatever m
+ *    is);
+ *  - a stripe with shard_lens[s] == 0 has its flags validated like any other
+ *    (more than m erasures refuses the call); it reads nothing, writes nothing,
+ *    gets RS_VERIFY_CLEAN and is counted in no stat.
+ * Refused with nothing launched or written (first_bad included): RS_EINVAL
+ * for a NULL ctx, NULL shard_lens with stripes > 0, everything the equal-length
+ * call refuses (NULL or misaligned table or first_bad, stripes >= 2^32, NULL
+ * erased for the repair), any length of 2^28 or more 16-byte columns, more
+ * than 2^31 - 1 blocks in all (a block is 256 columns of a stripe for one row
+ * group); RS_ENOT_ENOUGH when any stripe has more than m erasures.  RS_OK with
+ * nothing written for stripes == 0 or when every length is 0; m == 0: every
+ * stripe clean.
+ * When every stripe has the same non-zero length the call IS the equal-length
+ * call: same kernels, same stats (RSMI_SCRUB_LENS_FORCE=1, read once, for
+ * measurements only, keeps such a call on the per-stripe-length kernels).
+ * Otherwise compile-time twins of the verify, check and repair kernels
+ * (rs_kernel_name which = 14, 15, 16) serve it, whose blocks find their stripe
+ * by a search of a prefix sum of block counts; such a call counts one into
+ * RS_STAT_SCRUB_LENS_LAUNCHES and its degraded stripes that have bytes into
+ * RS_STAT_CHECK_STRIPES / RS_STAT_REPAIR_CHECKED, as the equal-length calls
+ * do.  RSMI_REPAIR_FUSED=0 does not apply to the mixed-length repair: there is
+ * no mixed-length unfused reconstruct, so it always runs the repair kernel's
+ * twin.  Enqueued on stream; returns when queued; safe from several threads on
+ * one ctx. */
+int rs_verify_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const size_t *shard_lens, size_t stripes,
+                        const uint8_t *erased, uint32_t *first_bad, void *stream);
+int rs_reconstruct_checked_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const size_t *shard_lens,
+                                     size_t stripes, const uint8_t *erased, uint32_t *first_bad, void *stream);
+
 /* Cached decode patterns held by the ctx (diagnostics / tests).  The cache
  * holds at most 2^20 patterns (RSMI_PATTERN_CAP); a call that would exceed
  * that evicts it whole, with no host synchronisation (the rebuilt rows wait
@@ -707,6 +761,7 @@ enum {
     RS_STAT_BATCH_LENS_PASSES = 24, /* GPU passes of rs_encode_batch_lens / rs_decode_batch_lens (one per staging group) */
     RS_STAT_COMBINE_LENS_LAUNCHES = 25, /* rs_combine_lens calls served by the per-job-length kernel (not by rs_combine's) */
     RS_STAT_REPAIR_CHECKED = 26,   /* stripes repaired and checked by the repair kernel (rs_reconstruct_checked*) */
+    RS_STAT_SCRUB_LENS_LAUNCHES = 27, /* rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls served by the per-stripe-length kernels */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -819,6 +874,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
  *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
  *    rs_verify_ptrs, rs_correct_columns_ptrs, rs_reconstruct_checked, rs_reconstruct_checked_ptrs,
+ *    rs_verify_ptrs_lens, rs_reconstruct_checked_ptrs_lens,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

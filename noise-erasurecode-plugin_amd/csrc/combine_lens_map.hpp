@@ -4,7 +4,9 @@
 // Shared by the kernel (rs_kernels.hip, rs_combine_kernel<.., VARLEN = true>)
 // and the host planner (combine_plan.cpp), so the CPU tests run the very
 // search the kernel runs: RSMI_HD is __host__ __device__ under hipcc and empty
-// under g++.
+// under g++.  The per-stripe-length twins of the verify, check and repair
+// kernels (rs_verify_ptrs_lens, rs_reconstruct_checked_ptrs_lens) and their
+// planner (scrub_lens_plan.cpp) use the same map, a "job" being a stripe.
 //
 // Job j of ncols[j] 16-byte columns owns the blocks
 //     [first_block[j], first_block[j + 1])

@@ -135,9 +135,20 @@ __device__ __forceinline__ void step_fence(uint32_t (&acc)[kRowsPerStep][4]) {
 // next to the survivor loads and become the accumulators' initial value, so
 // after the MACs an accumulator holds stored ^ recomputed and any set bit is
 // a mismatch; nothing is stored but one atomicMin per wave that saw one.
-template <int K, int MG, int BT, bool NT, bool VF = false>
+//
+// VARLEN (rs_verify_ptrs_lens, verify twin in pointer mode only): entry sv of
+// the stripe list has its own column count and shard length.  The block finds
+// sv by the search of lm->first_block[] that only `blk` feeds
+// (combine_lens_map.hpp: scalar loads, uniform across the block), in natural
+// block order, and takes every column bound -- the last column, the tail-lane
+// clamp, the end of the iterations, the chunk stride, the bytes that count --
+// from that entry.  a.iters is the most iterations any block runs; a.ncols16,
+// a.chunks and a.xcd are unused.  The equal-length instances take none of this.
+template <int K, int MG, int BT, bool NT, bool VF = false, bool VARLEN = false>
 __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uint32_t nblk, uint4* lds4,
-                                             uint32_t* first_bad = nullptr, uint32_t shard_len = 0) {
+                                             uint32_t* first_bad = nullptr, uint32_t shard_len = 0,
+                                             const ScrubLensTables* lm = nullptr) {
+    static_assert(!VARLEN || VF, "per-stripe lengths: the verify twin only");
     static_assert(MG % 2 == 0, "MG must be even");
     constexpr int TG = (MG + kRowsPerStep - 1) / kRowsPerStep;  // sub-steps per survivor
     constexpr int RL = MG - (TG - 1) * kRowsPerStep;            // rows in the last sub-step
@@ -156,12 +167,26 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
     uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
     uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * MG * 5);
 
+    // VARLEN: the block's place and its stripe's bounds, from the block map.
+    [[maybe_unused]] uint32_t v_grp = 0, v_chunk = 0, v_chunks = 0, v_ncols = 0, v_sv = 0;
+    if constexpr (VARLEN) {
+        const CombineBlock at = combine_lens_block(lm->first_block, lm->njobs, a.groups, blk);
+        v_sv = __builtin_amdgcn_readfirstlane(at.job);
+        v_grp = __builtin_amdgcn_readfirstlane(at.grp);
+        v_chunk = __builtin_amdgcn_readfirstlane(at.chunk);
+        v_chunks = __builtin_amdgcn_readfirstlane(at.chunks);
+        v_ncols = __builtin_amdgcn_readfirstlane(lm->ncols[v_sv]);
+        shard_len = __builtin_amdgcn_readfirstlane(lm->lens[v_sv]);
+    }
     // XCD-aware order (xcd.hpp): regions of a.xcd blocks per XCD in turn.
     uint64_t b = a.xcd ? xcd_block(blk, a.xcd, nblk) : blk;
-    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
+    const uint32_t grp = VARLEN ? v_grp : static_cast<uint32_t>(b % a.groups);
     b /= a.groups;
-    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
-    const uint64_t sv = b / a.chunks;
+    const uint32_t chunk = VARLEN ? v_chunk : static_cast<uint32_t>(b % a.chunks);
+    const uint64_t sv = VARLEN ? v_sv : b / a.chunks;
+    // The equal-length instances read both from the arguments where they did.
+    const uint32_t& chunks = VARLEN ? v_chunks : a.chunks;
+    const uint32_t& ncols16 = VARLEN ? v_ncols : a.ncols16;
     // Stripe descriptor = {stripe, pattern id << 8 | outputs} (one dependent
     // load); without a table it is stripe sv with a.desc0 (encode: pattern 0,
     // all m parity rows) -- a single-message decode then starts its pattern
@@ -225,7 +250,7 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
     } else {
         for (int i = threadIdx.x; i < k; i += BT) sptr[i] = shard(srcid ? srcid[i] : static_cast<uint32_t>(i));
     }
-    const uint32_t last = a.ncols16 - 1;
+    const uint32_t last = ncols16 - 1;
     // Survivor loads of the block's first iteration are issued before the
     // table build, so the prologue (pattern lookup, tables, barrier) overlaps
     // their HBM latency; with one iteration per block (the default) this is
@@ -234,7 +259,7 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
     // Iteration it of block `chunk` codes column chunk (it * chunks + chunk):
     // blocks running together stay on adjacent 4 KiB pieces of the same
     // shards (DRAM row locality) whatever the iteration count.
-    const uint32_t cstride = a.chunks * BT;
+    const uint32_t cstride = chunks * BT;
     const uint32_t col0 = chunk * BT + threadIdx.x;
     const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
     if constexpr (kRegPtrs) {
@@ -304,7 +329,7 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
 
     for (uint32_t it = 0; it < a.iters; ++it) {
         const uint32_t colbase = chunk * BT + it * cstride;
-        if (colbase >= a.ncols16) break;
+        if (colbase >= ncols16) break;
         RS_MEM_FENCE();
         const uint32_t col = colbase + threadIdx.x;
         const bool ok = col <= last;
@@ -360,7 +385,7 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
             // Software pipelining: the next iteration's survivor loads go out
             // before this iteration's stores.
             const uint32_t ncol = colbase + cstride + threadIdx.x;
-            if (it + 1 < a.iters && colbase + cstride < a.ncols16) {
+            if (it + 1 < a.iters && colbase + cstride < ncols16) {
                 const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
 #pragma unroll
                 for (int j = 0; j < K; ++j) xpre[j] = gload16<NT>(sp[j] + noff);
@@ -389,7 +414,7 @@ __device__ __forceinline__ void matmul_block(const MatArgs& a, uint32_t blk, uin
             const bool bad = byte < 16u;
             const uint64_t bal = __ballot(bad);
             if (bad && (bal & ((1ull << __lane_id()) - 1ull)) == 0) atomicMin(&first_bad[s], col * 16u + byte);
-            if (it + 1 < a.iters && colbase + cstride < a.ncols16) {
+            if (it + 1 < a.iters && colbase + cstride < ncols16) {
                 const uint32_t ncol = colbase + cstride + threadIdx.x;
                 load_stored((ncol <= last ? ncol : last) * 16u);
             }
@@ -413,6 +438,14 @@ template <int K, int MG, int BT, bool NT>
 __global__ __launch_bounds__(BT) void rs_verify_kernel(MatArgs a, uint32_t* first_bad, uint32_t shard_len) {
     extern __shared__ uint4 lds4[];
     matmul_block<K, MG, BT, NT, true>(a, blockIdx.x, gridDim.x, lds4, first_bad, shard_len);
+}
+
+// Its per-stripe-length twin (rs_verify_ptrs_lens; matmul_block<.., VARLEN>):
+// a.stripe_desc lists the stripes, lm carries their lengths and the block map.
+template <int K, int MG, int BT, bool NT>
+__global__ __launch_bounds__(BT) void rs_verify_lens_kernel(MatArgs a, uint32_t* first_bad, ScrubLensTables lm) {
+    extern __shared__ uint4 lds4[];
+    matmul_block<K, MG, BT, NT, true, true>(a, blockIdx.x, gridDim.x, lds4, first_bad, 0u, &lm);
 }
 
 // Scrub's locate step: wave i copies the n bytes of stripe pairs[i].x at byte
@@ -1143,8 +1176,17 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
 struct CheckPtrArgs : ReadArgs {
     const uint64_t* shard_ptrs;
 };
-template <int K, int MG, int BT, bool NT, bool PTRS = false>
-__global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, CheckPtrArgs, ReadArgs> a,
+// VARLEN (compile-time twin of the PTRS one, launch_check_lens): job b has
+// ncols[b] 16-byte columns and lens[b] bytes and owns the blocks
+// [first_block[b], first_block[b + 1]) of the grid; a.ncols16, a.chunks, a.xcd
+// and the shard_len argument are unused.
+struct CheckLensArgs : CheckPtrArgs {
+    const uint32_t* first_block;
+    const uint32_t* ncols;
+    const uint32_t* lens;
+};
+template <int K, int MG, int BT, bool NT, bool PTRS = false, bool VARLEN = false>
+__global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<VARLEN, CheckLensArgs, std::conditional_t<PTRS, CheckPtrArgs, ReadArgs>> a,
                                                       uint32_t* first_bad, uint32_t shard_len) {
     extern __shared__ uint4 lds4[];
     static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
@@ -1154,11 +1196,27 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
     uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
     uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * kStepWords);
 
-    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
-    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
-    b /= a.groups;
-    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
-    const uint64_t ji = b / a.chunks;
+    static_assert(!VARLEN || PTRS, "per-stripe lengths: the pointer placement only");
+    uint32_t grp, chunk, chunks, ncols16;
+    uint64_t ji;
+    if constexpr (VARLEN) {
+        // The job's own column count and shard length (see matmul_block).
+        const CombineBlock at = combine_lens_block(a.first_block, a.njobs, a.groups, blockIdx.x);
+        ji = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(at.job));
+        grp = __builtin_amdgcn_readfirstlane(at.grp);
+        chunk = __builtin_amdgcn_readfirstlane(at.chunk);
+        chunks = __builtin_amdgcn_readfirstlane(at.chunks);
+        ncols16 = __builtin_amdgcn_readfirstlane(a.ncols[ji]);
+        shard_len = __builtin_amdgcn_readfirstlane(a.lens[ji]);
+    } else {
+        uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+        grp = static_cast<uint32_t>(b % a.groups);
+        b /= a.groups;
+        chunk = static_cast<uint32_t>(b % a.chunks);
+        ji = b / a.chunks;
+        chunks = a.chunks;
+        ncols16 = a.ncols16;
+    }
     const ReadJob job = a.jobs[ji];
     // Stripe indices of a check fit 32 bits (plan_checks).
     const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe)));
@@ -1212,11 +1270,11 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
             }
         }
     }
-    const uint32_t last = a.ncols16 - 1;
+    const uint32_t last = ncols16 - 1;
     // Survivor loads of the block's first iteration go out before the table
     // build, as in matmul_block.
     uint4 xpre[kRegPtrs ? K : 1];
-    const uint32_t cstride = a.chunks * BT;
+    const uint32_t cstride = chunks * BT;
     const uint32_t col0 = chunk * BT + threadIdx.x;
     const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
     if constexpr (kRegPtrs) {
@@ -1270,7 +1328,7 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
 
     for (uint32_t it = 0; it < a.iters; ++it) {
         const uint32_t colbase = chunk * BT + it * cstride;
-        if (colbase >= a.ncols16) break;
+        if (colbase >= ncols16) break;
         RS_MEM_FENCE();
         const uint32_t col = colbase + threadIdx.x;
         const bool ok = col <= last;  // tail lanes re-read the last column (always in bounds) and do not report
@@ -1299,7 +1357,7 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
                 for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
             }
         }
-        const bool again = it + 1 < a.iters && colbase + cstride < a.ncols16;
+        const bool again = it + 1 < a.iters && colbase + cstride < ncols16;
         const uint32_t ncol = colbase + cstride + threadIdx.x;
         const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
         if constexpr (kRegPtrs) {
@@ -1352,8 +1410,8 @@ __global__ __launch_bounds__(BT) void rs_check_kernel(std::conditional_t<PTRS, C
 //
 // PTRS (compile-time twin, launch_repair_ptrs): as the check kernel's, and the
 // table entries of erased shards are loaded too: they are the destinations.
-template <int K, int MG, int BT, bool NT, bool PTRS = false>
-__global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, CheckPtrArgs, ReadArgs> a,
+template <int K, int MG, int BT, bool NT, bool PTRS = false, bool VARLEN = false>
+__global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<VARLEN, CheckLensArgs, std::conditional_t<PTRS, CheckPtrArgs, ReadArgs>> a,
                                                        uint32_t* first_bad, uint32_t shard_len) {
     extern __shared__ uint4 lds4[];
     static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
@@ -1363,11 +1421,27 @@ __global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, 
     uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
     uint8_t** sptr = reinterpret_cast<uint8_t**>(tw + k * kStepWords);
 
-    uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
-    const uint32_t grp = static_cast<uint32_t>(b % a.groups);
-    b /= a.groups;
-    const uint32_t chunk = static_cast<uint32_t>(b % a.chunks);
-    const uint64_t ji = b / a.chunks;
+    static_assert(!VARLEN || PTRS, "per-stripe lengths: the pointer placement only");
+    uint32_t grp, chunk, chunks, ncols16;
+    uint64_t ji;
+    if constexpr (VARLEN) {
+        // The job's own column count and shard length (see matmul_block).
+        const CombineBlock at = combine_lens_block(a.first_block, a.njobs, a.groups, blockIdx.x);
+        ji = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(at.job));
+        grp = __builtin_amdgcn_readfirstlane(at.grp);
+        chunk = __builtin_amdgcn_readfirstlane(at.chunk);
+        chunks = __builtin_amdgcn_readfirstlane(at.chunks);
+        ncols16 = __builtin_amdgcn_readfirstlane(a.ncols[ji]);
+        shard_len = __builtin_amdgcn_readfirstlane(a.lens[ji]);
+    } else {
+        uint64_t b = a.xcd ? xcd_block(blockIdx.x, a.xcd, gridDim.x) : blockIdx.x;
+        grp = static_cast<uint32_t>(b % a.groups);
+        b /= a.groups;
+        chunk = static_cast<uint32_t>(b % a.chunks);
+        ji = b / a.chunks;
+        chunks = a.chunks;
+        ncols16 = a.ncols16;
+    }
     const ReadJob job = a.jobs[ji];
     // Stripe indices of a repair fit 32 bits (plan_repairs).
     const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(job.stripe)));
@@ -1423,11 +1497,11 @@ __global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, 
             }
         }
     }
-    const uint32_t last = a.ncols16 - 1;
+    const uint32_t last = ncols16 - 1;
     // Survivor loads of the block's first iteration go out before the table
     // build, as in matmul_block.
     uint4 xpre[kRegPtrs ? K : 1];
-    const uint32_t cstride = a.chunks * BT;
+    const uint32_t cstride = chunks * BT;
     const uint32_t col0 = chunk * BT + threadIdx.x;
     const uint32_t off0 = (col0 <= last ? col0 : last) * 16u;
     if constexpr (kRegPtrs) {
@@ -1487,7 +1561,7 @@ __global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, 
 
     for (uint32_t it = 0; it < a.iters; ++it) {
         const uint32_t colbase = chunk * BT + it * cstride;
-        if (colbase >= a.ncols16) break;
+        if (colbase >= ncols16) break;
         RS_MEM_FENCE();
         const uint32_t col = colbase + threadIdx.x;
         const bool ok = col <= last;  // tail lanes re-read the last column (always in bounds): no report, no store
@@ -1516,7 +1590,7 @@ __global__ __launch_bounds__(BT) void rs_repair_kernel(std::conditional_t<PTRS, 
                 for (int w = 0; w < kStepWords; ++w) TA[w] = TB[w];
             }
         }
-        const bool again = it + 1 < a.iters && colbase + cstride < a.ncols16;
+        const bool again = it + 1 < a.iters && colbase + cstride < ncols16;
         const uint32_t ncol = colbase + cstride + threadIdx.x;
         const uint32_t noff = (ncol <= last ? ncol : last) * 16u;
         if constexpr (kRegPtrs) {
@@ -1733,8 +1807,12 @@ struct VerifyVariant {
     int K, MG;
     const char* name;
     void (*fn)(MatArgs, uint32_t*, uint32_t);
+    const char* lens_name;  // the per-stripe-length twin (pointer mode)
+    void (*lens_fn)(MatArgs, uint32_t*, ScrubLensTables);
 };
-#define RS_VERIFY(K, MG) {K, MG, "verify_K" #K "_MG" #MG "_B256", rs_verify_kernel<K, MG, kBlock, true>}
+#define RS_VERIFY(K, MG)                                                                                         \
+    {K, MG, "verify_K" #K "_MG" #MG "_B256", rs_verify_kernel<K, MG, kBlock, true>, "verify_K" #K "_MG" #MG "_B256_lens", \
+     rs_verify_lens_kernel<K, MG, kBlock, true>}
 const VerifyVariant kVerify[] = {
     RS_VERIFY(10, 4), RS_VERIFY(4, 4), RS_VERIFY(8, 6), RS_VERIFY(64, 16), RS_VERIFY(0, 4), RS_VERIFY(0, 8),
 };
@@ -1845,10 +1923,13 @@ struct CheckVariant {
     void (*fn)(ReadArgs, uint32_t*, uint32_t);
     const char* ptrs_name;  // the pointer-mode twin
     void (*ptrs_fn)(CheckPtrArgs, uint32_t*, uint32_t);
+    const char* lens_name;  // ... and its per-stripe-length twin
+    void (*lens_fn)(CheckLensArgs, uint32_t*, uint32_t);
 };
 #define RS_CHECK(K)                                                                                    \
     {K, "check_K" #K "_MG4_B256", rs_check_kernel<K, 4, kBlock, true>, "check_K" #K "_MG4_B256_ptrs", \
-     rs_check_kernel<K, 4, kBlock, true, true>}
+     rs_check_kernel<K, 4, kBlock, true, true>, "check_K" #K "_MG4_B256_ptrs_lens",                      \
+     rs_check_kernel<K, 4, kBlock, true, true, true>}
 const CheckVariant kCheck[] = {RS_CHECK(10), RS_CHECK(4), RS_CHECK(8), RS_CHECK(64), RS_CHECK(0)};
 #undef RS_CHECK
 
@@ -1865,10 +1946,13 @@ struct RepairVariant {
     void (*fn)(ReadArgs, uint32_t*, uint32_t);
     const char* ptrs_name;  // the pointer-mode twin
     void (*ptrs_fn)(CheckPtrArgs, uint32_t*, uint32_t);
+    const char* lens_name;  // ... and its per-stripe-length twin
+    void (*lens_fn)(CheckLensArgs, uint32_t*, uint32_t);
 };
 #define RS_REPAIR(K)                                                                                      \
     {K, "repair_K" #K "_MG4_B256", rs_repair_kernel<K, 4, kBlock, true>, "repair_K" #K "_MG4_B256_ptrs", \
-     rs_repair_kernel<K, 4, kBlock, true, true>}
+     rs_repair_kernel<K, 4, kBlock, true, true>, "repair_K" #K "_MG4_B256_ptrs_lens",                      \
+     rs_repair_kernel<K, 4, kBlock, true, true, true>}
 const RepairVariant kRepair[] = {RS_REPAIR(10), RS_REPAIR(4), RS_REPAIR(8), RS_REPAIR(64), RS_REPAIR(0)};
 #undef RS_REPAIR
 
@@ -1887,6 +1971,28 @@ const char* read_variant_name(int k) { return pick_read(k).name; }
 const char* check_variant_name(int k) { return pick_check(k).name; }
 
 const char* check_ptrs_variant_name(int k) { return pick_check(k).ptrs_name; }
+
+const char* check_lens_variant_name(int k) { return pick_check(k).lens_name; }
+
+hipError_t launch_check_lens(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad,
+                          const ScrubLensTables& t, uint32_t blocks, hipStream_t stream) {
+    if (a.njobs == 0 || blocks == 0) return hipSuccess;
+    if (!shard_ptrs || !t.first_block || !t.ncols || !t.lens || t.njobs != a.njobs) return hipErrorInvalidValue;
+    if (a.groups == 0 || a.iters == 0 || blocks > 0x7FFFFFFFu) return hipErrorInvalidConfiguration;
+    const CheckVariant& v = pick_check(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    CheckLensArgs la{};
+    static_cast<ReadArgs&>(la) = a;
+    la.ncols16 = 0;
+    la.chunks = 0;
+    la.xcd = 0;  // natural block order
+    la.shard_ptrs = shard_ptrs;
+    la.first_block = t.first_block;
+    la.ncols = t.ncols;
+    la.lens = t.lens;
+    hipLaunchKernelGGL(v.lens_fn, dim3(blocks), dim3(kBlock), lds, stream, la, first_bad, 0u);
+    return hipGetLastError();
+}
 
 hipError_t launch_check(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
     if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
@@ -1917,6 +2023,28 @@ hipError_t launch_check_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint
 const char* repair_variant_name(int k) { return pick_repair(k).name; }
 
 const char* repair_ptrs_variant_name(int k) { return pick_repair(k).ptrs_name; }
+
+const char* repair_lens_variant_name(int k) { return pick_repair(k).lens_name; }
+
+hipError_t launch_repair_lens(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad,
+                           const ScrubLensTables& t, uint32_t blocks, hipStream_t stream) {
+    if (a.njobs == 0 || blocks == 0) return hipSuccess;
+    if (!shard_ptrs || !t.first_block || !t.ncols || !t.lens || t.njobs != a.njobs) return hipErrorInvalidValue;
+    if (a.groups == 0 || a.iters == 0 || blocks > 0x7FFFFFFFu) return hipErrorInvalidConfiguration;
+    const RepairVariant& v = pick_repair(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    CheckLensArgs la{};
+    static_cast<ReadArgs&>(la) = a;
+    la.ncols16 = 0;
+    la.chunks = 0;
+    la.xcd = 0;  // natural block order
+    la.shard_ptrs = shard_ptrs;
+    la.first_block = t.first_block;
+    la.ncols = t.ncols;
+    la.lens = t.lens;
+    hipLaunchKernelGGL(v.lens_fn, dim3(blocks), dim3(kBlock), lds, stream, la, first_bad, 0u);
+    return hipGetLastError();
+}
 
 hipError_t launch_repair(const ReadArgs& a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
     if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
@@ -2189,6 +2317,30 @@ hipError_t launch_verify(MatArgs a, uint32_t* first_bad, uint32_t shard_len, hip
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     if (a.xcd == ~0u) a.xcd = a.chunks * a.groups;
     hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a, first_bad, shard_len);
+    return hipGetLastError();
+}
+
+uint32_t verify_row_groups(int k, int m) {
+    if (m <= 0) return 0;
+    const int mg = pick_verify(k, m).MG;
+    return static_cast<uint32_t>((m + mg - 1) / mg);
+}
+
+const char* verify_lens_variant_name(int k, int rows) { return pick_verify(k, rows).lens_name; }
+
+hipError_t launch_verify_lens(MatArgs a, uint32_t* first_bad, const ScrubLensTables& t, uint32_t blocks,
+                              hipStream_t stream) {
+    if (t.njobs == 0 || blocks == 0 || a.m == 0) return hipSuccess;
+    if (!a.shard_ptrs || !a.stripe_desc || !t.first_block || !t.ncols || !t.lens) return hipErrorInvalidValue;
+    if (a.iters == 0 || blocks > 0x7FFFFFFFu) return hipErrorInvalidConfiguration;
+    const VerifyVariant& v = pick_verify(static_cast<int>(a.k), static_cast<int>(a.m));
+    a.stripes = t.njobs;
+    a.ncols16 = 0;
+    a.chunks = 0;
+    a.xcd = 0;  // natural block order
+    a.groups = (a.m + v.MG - 1) / v.MG;
+    const size_t lds = static_cast<size_t>(a.k) * ((v.MG + 3) / 4) * kStepWords * 4 + a.k * sizeof(void*);
+    hipLaunchKernelGGL(v.lens_fn, dim3(blocks), dim3(kBlock), lds, stream, a, first_bad, t);
     return hipGetLastError();
 }
 

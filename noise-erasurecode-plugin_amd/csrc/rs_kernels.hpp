@@ -308,6 +308,38 @@ hipError_t launch_repair_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uin
                               hipStream_t stream);  // a: planned
 const char* repair_ptrs_variant_name(int k);  // "repair_K10_MG4_B256_ptrs" etc.
 
+// Per-stripe lengths for the pointer-mode scrub (rs_verify_ptrs_lens,
+// rs_reconstruct_checked_ptrs_lens; scrub_lens_plan.hpp): entry b of a
+// launch's list -- the stripe list of the verify kernel, the jobs of the check
+// and the repair kernel -- has ncols[b] >= 1 16-byte columns and lens[b] bytes
+// and owns the blocks [first_block[b], first_block[b + 1]) of the grid
+// (combine_lens_map.hpp), in natural block order.
+struct ScrubLensTables {
+    const uint32_t* first_block;  // [njobs + 1] (device)
+    const uint32_t* ncols;        // [njobs] (device)
+    const uint32_t* lens;         // [njobs] (device)
+    uint32_t njobs;
+};
+// Row groups per column chunk of the verify variant that serves (k, m).
+uint32_t verify_row_groups(int k, int m);
+// The per-stripe-length twin of launch_verify, pointer mode only: a.stripe_desc
+// lists t.njobs stripes {stripe index, 0 << 8 | m}, a.shard_ptrs is the table,
+// a.iters the most iterations a block runs (the plan's), and `blocks` the
+// plan's block count for verify_row_groups(k, m) row groups.
+hipError_t launch_verify_lens(MatArgs a, uint32_t* first_bad, const ScrubLensTables& t, uint32_t blocks,
+                              hipStream_t stream);
+const char* verify_lens_variant_name(int k, int rows);  // "verify_K10_MG4_B256_lens" etc.
+// The twins of launch_check_ptrs and launch_repair_ptrs: job b of a.jobs
+// (a.njobs == t.njobs) takes its columns and length from t.  a.groups =
+// ceil(max_j / 4) and a.iters are the plan's; a.ncols16, a.chunks and a.xcd are
+// unused.
+hipError_t launch_check_lens(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad,
+                             const ScrubLensTables& t, uint32_t blocks, hipStream_t stream);
+const char* check_lens_variant_name(int k);  // "check_K10_MG4_B256_ptrs_lens" etc.
+hipError_t launch_repair_lens(const ReadArgs& a, const uint64_t* shard_ptrs, uint32_t* first_bad,
+                              const ScrubLensTables& t, uint32_t blocks, hipStream_t stream);
+const char* repair_lens_variant_name(int k);  // "repair_K10_MG4_B256_ptrs_lens" etc.
+
 // Column gather of the scrub's locate step: for pairs[i] = {stripe, byte
 // offset} (device, offset < shard_len) out[i * n + id] = that byte of shard
 // id, for every shard of the stripe (a: strided layout, k, m).

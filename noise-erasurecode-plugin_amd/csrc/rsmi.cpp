@@ -42,6 +42,7 @@
 #include "pinned.hpp"
 #include "rs_kernels.hpp"
 #include "scrub.hpp"
+#include "scrub_lens_plan.hpp"
 #include "update_degraded_plan.hpp"
 #include "update_plan.hpp"
 
@@ -373,6 +374,7 @@ struct rs_ctx {
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     std::atomic<int64_t> repair_checked{0};                              // rs_reconstruct_checked: stripes of the repair kernel (rs_stat)
+    std::atomic<int64_t> scrub_lens_launches{0};                         // rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls the per-stripe-length kernels served
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
     std::atomic<int64_t> batch_lens_passes{0};                           // GPU passes of rs_encode_batch_lens / rs_decode_batch_lens
     std::atomic<int64_t> combine_lens_launches{0};                       // rs_combine_lens calls the per-job-length kernel served
@@ -1534,6 +1536,82 @@ int repair_checked(rs_ctx* c, const StripeView& v, const uint64_t* shard_ptrs, s
     if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
     return with_patterns(c, L, plan.flags.data(), plan.jobs.size(), s,
                          [&] { return launch_repair_stripes(c, L, v, stripes, plan, a, shard_ptrs, first_bad, s); });
+}
+
+// ------------------------------------------- per-stripe-length scrub ----
+// Launches a planned rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens
+// (repair) on stream s, as launch_check_stripes / launch_repair_stripes: with
+// jobs, pat_mu is held and L.pid holds the built pattern of every job.  One
+// upload carries the intact stripes' list, the job and entry tables, the jobs'
+// pattern ids and, for each of the two lists, its column counts, lengths and
+// block map; then first_bad's preset, the per-stripe-length twin of the verify
+// kernel over the intact stripes and that of the check or the repair kernel
+// over the jobs.
+int launch_scrub_lens(rs_ctx* c, Lease& L, size_t stripes, const rsmi::ScrubLensPlan& plan, bool repair,
+                      const uint64_t* shard_ptrs, uint32_t* first_bad, hipStream_t s) {
+    const rsmi::CheckPlan& cp = plan.checks;
+    const size_t nintact = cp.intact.size(), njobs = cp.jobs.size(), count = cp.entries.size();
+    // A list's three tables: ncols[n] | lens[n] | first_block[n + 1].
+    auto lens_bytes = [](size_t n) { return n ? (3 * n + 1) * sizeof(uint32_t) : size_t(0); };
+    const size_t job_off = round_up(nintact * sizeof(uint2), 16);
+    const size_t ent_off = job_off + njobs * sizeof(rsmi::ReadJob);
+    const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
+    const size_t ilens_off = pat_off + njobs * sizeof(uint32_t);
+    const size_t jlens_off = ilens_off + lens_bytes(nintact);
+    const size_t bytes = jlens_off + lens_bytes(njobs);
+    auto put_lens = [](uint8_t* at, const rsmi::ScrubLensList& l) {
+        const size_t n = l.ncols.size();
+        if (n == 0) return;
+        std::memcpy(at, l.ncols.data(), n * sizeof(uint32_t));
+        std::memcpy(at + n * sizeof(uint32_t), l.lens.data(), n * sizeof(uint32_t));
+        std::memcpy(at + 2 * n * sizeof(uint32_t), l.first_block.data(), (n + 1) * sizeof(uint32_t));
+    };
+    auto lens_tables = [](const uint8_t* at, size_t n) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(at);
+        return rsmi::ScrubLensTables{w + 2 * n, w, w + n, static_cast<uint32_t>(n)};
+    };
+    Tables t;
+    const int up = upload_tables(c, L, njobs, bytes, s, &t, [&](uint8_t* hb) {
+        uint2* desc = reinterpret_cast<uint2*>(hb);
+        for (size_t i = 0; i < nintact; ++i) desc[i] = make_uint2(cp.intact[i], static_cast<uint32_t>(c->m));
+        if (njobs > 0) {
+            std::memcpy(hb + job_off, cp.jobs.data(), njobs * sizeof(rsmi::ReadJob));
+            std::memcpy(hb + ent_off, cp.entries.data(), count * sizeof(rsmi::ReadEntry));
+            std::memcpy(hb + pat_off, L.pid.data(), njobs * sizeof(uint32_t));
+        }
+        put_lens(hb + ilens_off, plan.intact);
+        put_lens(hb + jlens_off, plan.jobs);
+    });
+    if (up != RS_OK) return up;
+    int rc = hipMemsetAsync(first_bad, 0xFF, stripes * sizeof(uint32_t), s) == hipSuccess ? RS_OK : RS_EDEVICE;
+    const StripeView v = StripeView::ptrs(0, 0);  // every length is its stripe's own
+    if (rc == RS_OK && c->m > 0 && nintact > 0) {
+        rsmi::MatArgs a = base_args(c, v, nintact);
+        set_patterns(c, 1, c->d_encpat.p, a);
+        a.stripe_desc = reinterpret_cast<const uint2*>(t.dev);
+        a.shard_ptrs = shard_ptrs;
+        a.iters = plan.iters;
+        rc = hip_status(rsmi::launch_verify_lens(a, first_bad, lens_tables(t.dev + ilens_off, nintact),
+                                                 plan.intact.blocks(), s));
+    }
+    if (rc == RS_OK && njobs > 0) {
+        rsmi::ReadArgs a = read_args(c, v, njobs);
+        a.groups = plan.jobs.groups;
+        a.iters = plan.iters;
+        a.coef = static_cast<const uint8_t*>(c->d_pcoef.p);
+        a.src = static_cast<const uint32_t*>(c->d_psrc.p);
+        a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev + job_off);
+        a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
+        a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
+        const rsmi::ScrubLensTables jt = lens_tables(t.dev + jlens_off, njobs);
+        rc = hip_status(repair ? rsmi::launch_repair_lens(a, shard_ptrs, first_bad, jt, plan.jobs.blocks(), s)
+                               : rsmi::launch_check_lens(a, shard_ptrs, first_bad, jt, plan.jobs.blocks(), s));
+    }
+    if (rc == RS_OK) {
+        (repair ? c->repair_checked : c->check_stripes) += static_cast<int64_t>(njobs);
+        ++c->scrub_lens_launches;
+    }
+    return finish_launch(c, L, s, t.waited, rc);
 }
 
 // ------------------------------------------------------ degraded update ----
@@ -3254,6 +3332,9 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 11) return rsmi::column_ptrs_variant_name(c->m);
     if (which == 12) return rsmi::repair_variant_name(c->k);
     if (which == 13) return rsmi::repair_ptrs_variant_name(c->k);
+    if (which == 14) return rsmi::verify_lens_variant_name(c->k, c->m);
+    if (which == 15) return rsmi::check_lens_variant_name(c->k);
+    if (which == 16) return rsmi::repair_lens_variant_name(c->k);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3319,6 +3400,7 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_BATCH_LENS_PASSES: return c->batch_lens_passes.load();
         case RS_STAT_COMBINE_LENS_LAUNCHES: return c->combine_lens_launches.load();
         case RS_STAT_REPAIR_CHECKED: return c->repair_checked.load();
+        case RS_STAT_SCRUB_LENS_LAUNCHES: return c->scrub_lens_launches.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3672,6 +3754,43 @@ int rs_combine_lens(rs_ctx* c, const rs_combine_job* jobs, size_t count, const s
     return combine_lens(c, *sc.L, plan, a, static_cast<hipStream_t>(stream));
 }
 
+namespace {
+// rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens (repair) behind the
+// NULL-ctx check.  The plan -- every refusal of the call -- is made before
+// anything is written or launched.
+int scrub_lens(rs_ctx* c, const uint64_t* shard_ptrs, const size_t* lens, size_t stripes, const uint8_t* erased,
+               uint32_t* first_bad, bool repair, hipStream_t s) {
+    if (stripes == 0) return RS_OK;
+    if (!lens) return RS_EINVAL;
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+    if (!first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u)) return RS_EINVAL;
+    if (repair && !erased) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the stripe list
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    rsmi::ScrubLensPlan plan;
+    const int rc = rsmi::plan_scrub_lens(c->k, c->n, stripes, erased, lens, repair, rsmi::verify_row_groups(c->k, c->m),
+                                         rsmi::combine_iters_cap(), &plan);
+    if (rc != RS_OK) return rc;
+    if (plan.live == 0) return RS_OK;  // no stripe has any bytes
+    // One non-zero length for every stripe: the call is the equal-length call,
+    // kernels and all.  RSMI_SCRUB_LENS_FORCE=1 (measurements only) keeps it on
+    // the twins.
+    static const bool force = [] {
+        const char* e = std::getenv("RSMI_SCRUB_LENS_FORCE");
+        return e && std::atoi(e) != 0;
+    }();
+    if (!force && plan.len_all != 0)
+        return repair ? rs_reconstruct_checked_ptrs(c, shard_ptrs, plan.len_all, stripes, erased, first_bad, s)
+                      : rs_verify_ptrs(c, shard_ptrs, plan.len_all, stripes, erased, first_bad, s);
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    Lease& L = *sc.L;
+    return with_patterns(c, L, plan.checks.flags.data(), plan.checks.jobs.size(), s, [&] {
+        return launch_scrub_lens(c, L, stripes, plan, repair, shard_ptrs, first_bad, s);
+    });
+}
+}  // namespace
+
 int rs_reconstruct_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
                         void* stream) {
     if (!c || !erased || !shard_ptrs) return RS_EINVAL;
@@ -3723,6 +3842,18 @@ int rs_reconstruct_checked_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t le
     if (!route(c, shard_ptrs)) return RS_EINVAL;
     return repair_checked(c, StripeView::ptrs(round_up(len, 16), len), shard_ptrs, stripes, erased, first_bad,
                           static_cast<hipStream_t>(stream));
+}
+
+int rs_verify_ptrs_lens(rs_ctx* c, const uint64_t* shard_ptrs, const size_t* lens, size_t stripes, const uint8_t* erased,
+                        uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    return scrub_lens(c, shard_ptrs, lens, stripes, erased, first_bad, false, static_cast<hipStream_t>(stream));
+}
+
+int rs_reconstruct_checked_ptrs_lens(rs_ctx* c, const uint64_t* shard_ptrs, const size_t* lens, size_t stripes,
+                                     const uint8_t* erased, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    return scrub_lens(c, shard_ptrs, lens, stripes, erased, first_bad, true, static_cast<hipStream_t>(stream));
 }
 
 int rs_correct_columns_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

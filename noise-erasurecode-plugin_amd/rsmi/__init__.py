@@ -40,6 +40,7 @@ EXPORTS = (
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_ptrs", "rs_correct_columns_ptrs",
     "rs_reconstruct_checked", "rs_reconstruct_checked_ptrs",
+    "rs_verify_ptrs_lens", "rs_reconstruct_checked_ptrs_lens",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
     "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
@@ -175,6 +176,8 @@ def _lib() -> ctypes.CDLL:
             "rs_correct_degraded": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_reconstruct_checked": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp, vp]),
             "rs_reconstruct_checked_ptrs": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+            "rs_verify_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, vp, vp]),
+            "rs_reconstruct_checked_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, vp, vp]),
             "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
             "rs_combine_lens": (i32, [vp, ctypes.POINTER(CombineJob), sz, ctypes.POINTER(sz), vp]),
@@ -346,8 +349,10 @@ class FEC:
     def kernel_name(self, which: int = 0) -> str:
         """Kernel serving encode (0), reconstruct (1), verify (2), update
         (3), degraded read (4), degraded check (5), combine (6), degraded
-        update (7), column scrub (8) or combine_lens of mixed lengths (9):
-        diagnostics."""
+        update (7), column scrub (8) or combine_lens of mixed lengths (9);
+        10 to 13 the pointer-mode check and column kernels and the repair
+        kernels, 14 to 16 the per-stripe-length twins of verify, check and
+        repair (verify_ptrs_lens, reconstruct_checked_ptrs_lens): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -740,6 +745,44 @@ class FEC:
                                                   ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None,
                                                   stream or None), "rs_reconstruct_checked_ptrs")
 
+    def _stripe_lens(self, shard_lens: Sequence[int], stripes: int):
+        if len(shard_lens) != stripes:
+            raise RSError(RS_EINVAL, "shard_lens must hold one length per stripe")
+        if isinstance(shard_lens, ctypes.Array):
+            return shard_lens
+        return (ctypes.c_size_t * max(stripes, 1))(*shard_lens)
+
+    def verify_ptrs_lens(self, shard_ptrs_dev: int, shard_lens: Sequence[int], stripes: int, first_bad_ptr: int,
+                         erased: Optional[bytes] = None, stream: int = 0) -> None:
+        """rs_verify_ptrs_lens: verify_ptrs where stripe s has shard_lens[s]
+        bytes per shard (a sequence, or a ctypes c_size_t array for a caller
+        that repeats a large one).  Bytes past a stripe's length are neither
+        read past its last 16-byte column nor compared; a stripe of length 0
+        is clean.  Enqueued on stream."""
+        lens = self._stripe_lens(shard_lens, stripes)
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_verify_ptrs_lens(self._h, shard_ptrs_dev or None, lens, stripes,
+                                          ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None, stream or None),
+               "rs_verify_ptrs_lens")
+
+    def reconstruct_checked_ptrs_lens(self, shard_ptrs_dev: int, shard_lens: Sequence[int], stripes: int,
+                                      erased: bytes, first_bad_ptr: int, stream: int = 0) -> None:
+        """rs_reconstruct_checked_ptrs_lens: reconstruct_checked_ptrs where
+        stripe s has shard_lens[s] bytes per shard, as verify_ptrs_lens.  The
+        slot of an erased shard of stripe s receives round_up(shard_lens[s],
+        16) bytes.  Enqueued on stream."""
+        lens = self._stripe_lens(shard_lens, stripes)
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        buf = ctypes.c_char_p(bytes(erased))
+        _check(_lib().rs_reconstruct_checked_ptrs_lens(self._h, shard_ptrs_dev or None, lens, stripes,
+                                                       ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None,
+                                                       stream or None), "rs_reconstruct_checked_ptrs_lens")
+
     def correct_columns_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int,
                              erased: Optional[bytes] = None, stream: int = 0):
         """rs_correct_columns_ptrs: correct_columns for shards at the device
@@ -772,7 +815,7 @@ class FEC:
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
      STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES, STAT_BATCH_LENS_PASSES,
-     STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED) = range(27)
+     STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED, STAT_SCRUB_LENS_LAUNCHES) = range(28)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
