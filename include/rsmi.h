@@ -92,7 +92,9 @@ const char *rs_strerror(int status);
  * twins of which = 2, 10 and 13 that serve rs_verify_ptrs_lens and
  * rs_reconstruct_checked_ptrs_lens calls of mixed lengths, e.g.
  * "verify_K10_MG4_B256_lens", "check_K10_MG4_B256_ptrs_lens" and
- * "repair_K10_MG4_B256_ptrs_lens". */
+ * "repair_K10_MG4_B256_ptrs_lens"; which = 17: the per-job-length twin of
+ * which = 11 that serves rs_correct_columns_ptrs_lens calls of mixed lengths,
+ * e.g. "columns_MG4_B256_ptrs_lens" ("none" for m > 16). */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -724,6 +726,65 @@ int rs_verify_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const size_t *s
 int rs_reconstruct_checked_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const size_t *shard_lens,
                                      size_t stripes, const uint8_t *erased, uint32_t *first_bad, void *stream);
 
+/* rs_correct_columns_ptrs for stripes that each have a shard length of their
+ * own: the middle step of the recipe above for a store of objects of different
+ * sizes, in one call.  shard_ptrs, erased, status and corrected are those of
+ * rs_correct_columns_ptrs; shard_lens is a HOST array of `stripes` lengths and
+ * is not retained.  Stripe s is treated exactly as rs_correct_columns_ptrs
+ * would treat it if it were called on that stripe alone with shard_len =
+ * shard_lens[s]:
+ *  - every byte column o < shard_lens[s] is decoded on its own, within
+ *    floor((r - k) / 2) of the r present shares; status[s] (HOST int[stripes],
+ *    may be NULL) and corrected[s * n + i] (HOST uint32[stripes * n], may be
+ *    NULL) mean what they mean there: RS_OK or RS_ETOO_MANY_ERRORS (a column
+ *    beyond the radius, which is left alone while the others are corrected, or
+ *    an inconsistent stripe with r - k < 2, which is not written at all), and
+ *    the bytes changed in shard i; the call returns RS_ETOO_MANY_ERRORS when
+ *    any stripe failed;
+ *  - the same sequence: verify, one column launch over the inconsistent
+ *    stripes only, verify of those stripes again; synchronous, two host round
+ *    trips;
+ *  - at most round_up(shard_lens[s], 16) bytes of a present shard of stripe s
+ *    are read;
+ *  - bytes at or beyond shard_lens[s] are never decoded and never written, so a
+ *    wrong byte in [shard_lens[s], round_up(shard_lens[s], 16)) is not an error
+ *    (padding a short object to a longer length is therefore no substitute:
+ *    the bytes behind its length are no part of a codeword);
+ *  - clean stripes are never written, table entries of erased shards are never
+ *    loaded, the table itself is never written; the ranges of the present
+ *    shards must not overlap (not checked);
+ *  - a stripe with shard_lens[s] == 0 has its flags validated like any other;
+ *    it reads nothing, writes nothing, ends RS_OK with zero corrected and is
+ *    counted in no stat.
+ * Refused with nothing launched and nothing written (status and corrected
+ * included): RS_EINVAL for a NULL ctx (before any HIP call), NULL shard_lens
+ * with stripes > 0, a NULL or misaligned table, stripes >= 2^32, any length of
+ * 2^28 or more 16-byte columns, m > 16, more than 2^31 - 1 blocks in either
+ * verify launch (rs_verify_ptrs_lens' bound), or more than 2^31 - 1 blocks in
+ * the worst-case column launch, the sum over the stripes that have bytes of
+ * ceil(ncols_s / 256) with ncols_s = round_up(shard_lens[s], 16) / 16 -- checked
+ * up front, so the refusal does not depend on which stripes turn out
+ * inconsistent; RS_ENOT_ENOUGH when any stripe, with or without bytes, has more
+ * than m erasures.  RS_OK for stripes == 0; RS_OK with status all RS_OK and
+ * corrected all 0 when every length is 0 or m == 0.
+ * When every stripe has the same non-zero length the call IS
+ * rs_correct_columns_ptrs: it calls it, same kernels, same stats
+ * (RSMI_COLUMN_LENS_FORCE=1, read once, for measurements only, keeps such a
+ * call on the twin).  Otherwise both verifies are rs_verify_ptrs_lens' launches
+ * and count into RS_STAT_CHECK_STRIPES / RS_STAT_SCRUB_LENS_LAUNCHES exactly as
+ * those calls would (the second is planned over the inconsistent stripes only),
+ * and the column launch runs the per-job-length twin of the pointer-mode column
+ * kernel (rs_kernel_name which = 17), whose blocks find their stripe by a
+ * search of a prefix sum of block counts; it counts one into
+ * RS_STAT_COLUMN_LENS_LAUNCHES, its stripes into RS_STAT_COLUMN_STRIPES and the
+ * bytes it changed into RS_STAT_COLUMN_BYTES.  Safe from several threads on one
+ * ctx. */
+int rs_correct_columns_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const size_t *shard_lens,
+                                 size_t stripes, const uint8_t *erased /* HOST, may be NULL */,
+                                 int *status /* HOST int[stripes], may be NULL */,
+                                 uint32_t *corrected /* HOST uint32[stripes*n], may be NULL */,
+                                 void *stream);
+
 /* Cached decode patterns held by the ctx (diagnostics / tests).  The cache
  * holds at most 2^20 patterns (RSMI_PATTERN_CAP); a call that would exceed
  * that evicts it whole, with no host synchronisation (the rebuilt rows wait
@@ -762,6 +823,7 @@ enum {
     RS_STAT_COMBINE_LENS_LAUNCHES = 25, /* rs_combine_lens calls served by the per-job-length kernel (not by rs_combine's) */
     RS_STAT_REPAIR_CHECKED = 26,   /* stripes repaired and checked by the repair kernel (rs_reconstruct_checked*) */
     RS_STAT_SCRUB_LENS_LAUNCHES = 27, /* rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls served by the per-stripe-length kernels */
+    RS_STAT_COLUMN_LENS_LAUNCHES = 28, /* column launches of rs_correct_columns_ptrs_lens served by the per-job-length twin (not by rs_correct_columns_ptrs') */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -874,7 +936,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    rs_verify_stripes, rs_correct_stripes, rs_update_stripes, rs_read_stripes,
  *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
  *    rs_verify_ptrs, rs_correct_columns_ptrs, rs_reconstruct_checked, rs_reconstruct_checked_ptrs,
- *    rs_verify_ptrs_lens, rs_reconstruct_checked_ptrs_lens,
+ *    rs_verify_ptrs_lens, rs_reconstruct_checked_ptrs_lens, rs_correct_columns_ptrs_lens,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

@@ -4,6 +4,7 @@
 #include "column_correct.hpp"
 
 #include "column_decode.hpp"
+#include "combine_lens_map.hpp"
 #include "gf_device.hpp"
 
 namespace rsmi {
@@ -43,6 +44,14 @@ static_assert(kColSources * kColumnMaxSyn * 5 * 4 <= kColRegion, "tables fit the
 // shard's position in the present list: phase A's loads and phase B's byte
 // stores read that array, never the table, and the table entries of shards
 // outside the present list are never loaded.
+//
+// VARLEN (compile-time twin of the PTRS twin, rs_correct_columns_ptrs_lens):
+// every job has a length of its own.  A block finds its {job, chunk} by the
+// search of combine_lens_map.hpp (groups = 1) over a.first_block -- job j owns
+// ceil(ncols_j / 256) blocks, one 4 KiB chunk each, as above -- and takes the
+// job's column count and length from a.job_ncols / a.job_lens where the others
+// take a.ncols16 / a.shard_len.  All of it is uniform: scalar loads and
+// compares, no LDS and no lane state beyond the PTRS twin's.
 
 // The twin's address array; only the PTRS instantiations allocate it.
 template <bool PTRS>
@@ -55,8 +64,9 @@ __device__ __forceinline__ uint64_t* column_ptr_lds() {
     }
 }
 
-template <int MG, bool PTRS = false>
+template <int MG, bool PTRS = false, bool VARLEN = false>
 __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
+    static_assert(PTRS || !VARLEN, "per-job lengths: pointer placement only");
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
     __shared__ uint8_t s_ids[256];
@@ -65,8 +75,19 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
     __shared__ uint32_t s_cnt[256];
     __shared__ uint4 s_region[kColRegion / 16];
     const int tid = static_cast<int>(threadIdx.x);
-    const uint32_t jb = blockIdx.x / a.chunks;
-    const uint32_t chunk = blockIdx.x - jb * a.chunks;
+    uint32_t jb, chunk, ncols16, shard_len;
+    if constexpr (VARLEN) {
+        const CombineBlock cb = combine_lens_block(a.first_block, a.njobs, 1u, blockIdx.x);
+        jb = cb.job;
+        chunk = cb.chunk;
+        ncols16 = a.job_ncols[jb];
+        shard_len = a.job_lens[jb];
+    } else {
+        jb = blockIdx.x / a.chunks;
+        chunk = blockIdx.x - jb * a.chunks;
+        ncols16 = a.ncols16;
+        shard_len = a.shard_len;
+    }
     const uint4 job = a.jobs[jb];
     const uint64_t stripe = __builtin_amdgcn_readfirstlane(job.x);
     const int r = static_cast<int>(__builtin_amdgcn_readfirstlane(job.z));
@@ -97,7 +118,7 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
         }
     };
     const uint32_t col = chunk * kColBlock + static_cast<uint32_t>(tid);
-    const bool ok = col < a.ncols16;
+    const bool ok = col < ncols16;
     const uint32_t off = col * 16u;
 
     uint32_t* tw = reinterpret_cast<uint32_t*>(s_region);
@@ -163,7 +184,7 @@ __global__ __launch_bounds__(kColBlock) void rs_column_kernel(ColArgs a) {
     for (uint32_t b = 0; b < 16u; ++b) {
         if (!ok || any == 0u) break;
         const uint32_t o = off + b;
-        if (o >= a.shard_len) break;  // the pad to 16 is not decoded
+        if (o >= shard_len) break;  // the pad to 16 is not decoded
         const uint32_t wsel = b >> 2, sh = (b & 3u) * 8u;
         uint32_t nz = 0u;
 #pragma unroll
@@ -223,6 +244,20 @@ hipError_t launch_column_correct(const ColArgs& a, int m, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_column_correct_lens(const ColArgs& a, int m, uint32_t blocks, hipStream_t stream) {
+    if (a.njobs == 0 || blocks == 0) return hipSuccess;
+    if (!column_correct_supported(m) || !a.shard_ptrs || !a.first_block || !a.job_ncols || !a.job_lens ||
+        blocks > 0x7FFFFFFFu)
+        return hipErrorInvalidValue;
+    const dim3 grid(blocks), block(kColBlock);
+    switch (column_mg(m)) {
+        case 4: hipLaunchKernelGGL((rs_column_kernel<4, true, true>), grid, block, 0, stream, a); break;
+        case 8: hipLaunchKernelGGL((rs_column_kernel<8, true, true>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((rs_column_kernel<16, true, true>), grid, block, 0, stream, a); break;
+    }
+    return hipGetLastError();
+}
+
 const char* column_variant_name(int m) {
     if (!column_correct_supported(m)) return "none";
     switch (column_mg(m)) {
@@ -238,6 +273,15 @@ const char* column_ptrs_variant_name(int m) {
         case 4: return "columns_MG4_B256_ptrs";
         case 8: return "columns_MG8_B256_ptrs";
         default: return "columns_MG16_B256_ptrs";
+    }
+}
+
+const char* column_lens_variant_name(int m) {
+    if (!column_correct_supported(m)) return "none";
+    switch (column_mg(m)) {
+        case 4: return "columns_MG4_B256_ptrs_lens";
+        case 8: return "columns_MG8_B256_ptrs_lens";
+        default: return "columns_MG16_B256_ptrs_lens";
     }
 }
 

@@ -33,6 +33,7 @@
 #include "check_plan.hpp"
 #include "column_correct.hpp"
 #include "column_decode.hpp"
+#include "column_lens_plan.hpp"
 #include "combine_plan.hpp"
 #include "device_set.hpp"
 #include "gf256.hpp"
@@ -374,7 +375,8 @@ struct rs_ctx {
     std::atomic<int64_t> read_regenerated{0}, read_copied{0};            // rs_read_stripes (rs_stat)
     std::atomic<int64_t> check_stripes{0}, scrub_regenerated{0};         // rs_verify_degraded / rs_correct_degraded (rs_stat)
     std::atomic<int64_t> repair_checked{0};                              // rs_reconstruct_checked: stripes of the repair kernel (rs_stat)
-    std::atomic<int64_t> scrub_lens_launches{0};                         // rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls the per-stripe-length kernels served
+    std::atomic<int64_t> column_lens_launches{0};                        // column launches of rs_correct_columns_ptrs_lens served by the per-job-length twin
+    std::atomic<int64_t> scrub_lens_launches{0};                        // rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls the per-stripe-length kernels served
     std::atomic<int64_t> combine_jobs{0}, combine_rows{0};               // rs_combine (rs_stat)
     std::atomic<int64_t> batch_lens_passes{0};                           // GPU passes of rs_encode_batch_lens / rs_decode_batch_lens
     std::atomic<int64_t> combine_lens_launches{0};                       // rs_combine_lens calls the per-job-length kernel served
@@ -2010,6 +2012,127 @@ int correct_columns(rs_ctx* c, Lease& L, const StripeView& v, size_t stripes, co
     return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
 }
 
+// rs_correct_columns_ptrs_lens on stream s with lease L, behind its refusals
+// (1 <= m <= 16, some stripe has bytes, not all of one length): correct_columns
+// with every stripe at its own length.  `first` is plan_scrub_lens' plan of the
+// verify of all stripes, `cp` plan_column_lens' plan of the call; erased may be
+// nullptr.  Both verifies are rs_verify_ptrs_lens' launches (launch_scrub_lens
+// under with_patterns) with first_bad at the head of the lease's scrub
+// workspace; the second covers the jobs' stripes only: it is planned over
+// lengths in which every other stripe has none, so those read nothing and come
+// back clean.  Workspace behind first_bad u32 [stripes], once the first verify
+// has named the nd jobs and their npat erasure sets:
+//   | jobs uint4 [nd] | tables [npat][column_table_bytes(n)]
+//   | ncols u32 [nd] | lens u32 [nd] | first_block u32 [nd + 1]
+//   | counts u32 [nd * n] | fail u32 [nd]
+// One copy up (jobs to first_block), one copy down (counts and fail), two host
+// round trips, as correct_columns.
+int correct_columns_lens(rs_ctx* c, Lease& L, size_t stripes, const uint8_t* erased, const size_t* lens,
+                         const rsmi::ColumnLensPlan& cp, const rsmi::ScrubLensPlan& first, const uint64_t* shard_ptrs,
+                         int* status, uint32_t* corrected, hipStream_t s) {
+    static_assert(sizeof(rsmi::ColumnLensJob) == sizeof(uint4), "the kernel loads a job as a uint4");
+    const size_t n = static_cast<size_t>(c->n);
+    const size_t jobs_off = round_up(stripes * sizeof(uint32_t), 16);
+    L.begin(s);
+    if (!L.st_scrub.acquire(jobs_off) || !L.d_scrub.reserve_on(jobs_off, s)) return RS_ENOMEM;
+    uint8_t* hb = static_cast<uint8_t*>(L.st_scrub.p);
+    uint8_t* db = static_cast<uint8_t*>(L.d_scrub.p);
+    // Every exit records the lease's last device use.
+    struct End {
+        Lease& L;
+        hipStream_t s;
+        ~End() { L.end(s); }
+    } end_guard{L, s};
+
+    // A planned verify on s; the verdicts of all stripes are at db afterwards.
+    auto verify = [&](const rsmi::ScrubLensPlan& plan) -> int {
+        return with_patterns(c, L, plan.checks.flags.data(), plan.checks.jobs.size(), s, [&] {
+            return launch_scrub_lens(c, L, stripes, plan, false, shard_ptrs, reinterpret_cast<uint32_t*>(db), s);
+        });
+    };
+    int rc = verify(first);
+    if (rc != RS_OK) return rc;
+    if (hipMemcpyAsync(hb, db, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return RS_EDEVICE;
+
+    bool failed = false;
+    auto give_up = [&](uint32_t i) {
+        if (status) status[i] = RS_ETOO_MANY_ERRORS;
+        failed = true;
+    };
+    rsmi::ColumnLensJobs cj;
+    rsmi::plan_column_lens_jobs(c->k, c->n, stripes, erased, lens, cp, reinterpret_cast<const uint32_t*>(hb), &cj);
+    for (uint32_t i : cj.hopeless) give_up(i);  // inconsistent without a radius
+    const size_t nd = cj.jobs.size();
+    if (nd == 0) return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+    rsmi::ScrubLensPlan second;
+    rc = rsmi::plan_scrub_lens(c->k, c->n, stripes, erased, cj.masked.data(), false, rsmi::verify_row_groups(c->k, c->m),
+                               first.iters, &second);
+    if (rc != RS_OK) return rc;
+
+    const size_t tb = rsmi::column_table_bytes(c->n);
+    const size_t tab_off = jobs_off + nd * sizeof(uint4);
+    const size_t ncols_off = tab_off + cj.sets.size() * tb;  // tb is a multiple of 16
+    const size_t lens_off = ncols_off + nd * sizeof(uint32_t);
+    const size_t fblk_off = lens_off + nd * sizeof(uint32_t);
+    const size_t cnt_off = fblk_off + (nd + 1) * sizeof(uint32_t);
+    const size_t fail_off = cnt_off + nd * n * sizeof(uint32_t);
+    const size_t bytes = fail_off + nd * sizeof(uint32_t);
+    // Growing the workspace drops the verdicts, which the host is done with.
+    if (!L.st_scrub.acquire(bytes) || !L.d_scrub.reserve_on(bytes, s)) return RS_ENOMEM;
+    hb = static_cast<uint8_t*>(L.st_scrub.p);
+    db = static_cast<uint8_t*>(L.d_scrub.p);
+    std::memcpy(hb + jobs_off, cj.jobs.data(), nd * sizeof(uint4));
+    for (size_t t = 0; t < cj.sets.size(); ++t) rsmi::column_tables(c->n, cj.sets[t].data(), hb + tab_off + t * tb);
+    std::memcpy(hb + ncols_off, cj.ncols.data(), nd * sizeof(uint32_t));
+    std::memcpy(hb + lens_off, cj.lens.data(), nd * sizeof(uint32_t));
+    std::memcpy(hb + fblk_off, cj.first_block.data(), (nd + 1) * sizeof(uint32_t));
+
+    rsmi::ColArgs a{};
+    a.k = static_cast<uint32_t>(c->k);
+    a.n = static_cast<uint32_t>(c->n);
+    a.njobs = static_cast<uint32_t>(nd);
+    a.shard_ptrs = shard_ptrs;
+    a.jobs = reinterpret_cast<const uint4*>(db + jobs_off);
+    a.tables = db + tab_off;
+    a.gf = dev_enc(c) + n * static_cast<size_t>(c->k);
+    a.counts = reinterpret_cast<uint32_t*>(db + cnt_off);
+    a.fail = reinterpret_cast<uint32_t*>(db + fail_off);
+    a.job_ncols = reinterpret_cast<const uint32_t*>(db + ncols_off);
+    a.job_lens = reinterpret_cast<const uint32_t*>(db + lens_off);
+    a.first_block = reinterpret_cast<const uint32_t*>(db + fblk_off);
+    hipError_t e = hipMemcpyAsync(db + jobs_off, hb + jobs_off, cnt_off - jobs_off, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(db + cnt_off, 0, bytes - cnt_off, s);
+    if (e == hipSuccess) e = rsmi::launch_column_correct_lens(a, c->m, cj.blocks(), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hb + cnt_off, db + cnt_off, bytes - cnt_off, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return RS_EDEVICE;
+    c->column_stripes += static_cast<int64_t>(nd);
+    ++c->column_lens_launches;
+
+    // The same stripes again: one still inconsistent has a hopeless column,
+    // whatever its fail word says.
+    rc = verify(second);
+    if (rc != RS_OK) return rc;
+    if (hipMemcpyAsync(hb, db, stripes * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return RS_EDEVICE;
+    const uint32_t* h_fb = reinterpret_cast<const uint32_t*>(hb);
+    const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(hb + cnt_off);
+    const uint32_t* h_fail = reinterpret_cast<const uint32_t*>(hb + fail_off);
+    int64_t changed = 0;
+    for (size_t j = 0; j < nd; ++j) {
+        const uint32_t i = cj.jobs[j].stripe;
+        for (size_t id = 0; id < n; ++id) {
+            changed += h_cnt[j * n + id];
+            if (corrected) corrected[i * n + id] = h_cnt[j * n + id];
+        }
+        if (h_fail[j] != 0 || h_fb[i] != RS_VERIFY_CLEAN) give_up(i);
+    }
+    c->column_bytes += changed;
+    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+}
+
 // Holds the least busy member of a device set for one call.
 struct SetPick {
     rsmi::DeviceSet* s;
@@ -3335,6 +3458,7 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 14) return rsmi::verify_lens_variant_name(c->k, c->m);
     if (which == 15) return rsmi::check_lens_variant_name(c->k);
     if (which == 16) return rsmi::repair_lens_variant_name(c->k);
+    if (which == 17) return rsmi::column_lens_variant_name(c->m);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3401,6 +3525,7 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_COMBINE_LENS_LAUNCHES: return c->combine_lens_launches.load();
         case RS_STAT_REPAIR_CHECKED: return c->repair_checked.load();
         case RS_STAT_SCRUB_LENS_LAUNCHES: return c->scrub_lens_launches.load();
+        case RS_STAT_COLUMN_LENS_LAUNCHES: return c->column_lens_launches.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -3881,6 +4006,45 @@ int rs_correct_columns_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, s
     if (sc.error() != RS_OK) return sc.error();
     return correct_columns(c, *sc.L, StripeView::ptrs(round_up(len, 16), len), stripes, degraded ? erased : nullptr,
                            shard_ptrs, status, corrected, static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_columns_ptrs_lens(rs_ctx* c, const uint64_t* shard_ptrs, const size_t* lens, size_t stripes,
+                                 const uint8_t* erased, int* status, uint32_t* corrected, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0) return RS_OK;
+    if (!lens) return RS_EINVAL;
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull) return RS_EINVAL;  // 32-bit stripe indices in the job list
+    if (c->m > rsmi::kColumnMaxSyn) return RS_EINVAL;  // the kernel keeps at most 16 syndromes per column
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    // Every refusal -- the lengths, the erasure counts, the worst-case grid of
+    // the column launch, the grids of the verifies -- before anything is
+    // written or launched.  The second verify covers a subset of the first's
+    // stripes, each at the same length: its grid is no larger.
+    rsmi::ColumnLensPlan cp;
+    int rc = rsmi::plan_column_lens(c->k, c->n, stripes, erased, lens, &cp);
+    if (rc != RS_OK) return rc;
+    rsmi::ScrubLensPlan first;
+    rc = rsmi::plan_scrub_lens(c->k, c->n, stripes, cp.degraded ? erased : nullptr, lens, false,
+                               rsmi::verify_row_groups(c->k, c->m), rsmi::combine_iters_cap(), &first);
+    if (rc != RS_OK) return rc;
+    // One non-zero length for every stripe: the call is rs_correct_columns_ptrs,
+    // kernels and all.  RSMI_COLUMN_LENS_FORCE=1 (measurements only) keeps it on
+    // the twin.
+    static const bool force = [] {
+        const char* e = std::getenv("RSMI_COLUMN_LENS_FORCE");
+        return e && std::atoi(e) != 0;
+    }();
+    if (!force && cp.len_all != 0)
+        return rs_correct_columns_ptrs(c, shard_ptrs, cp.len_all, stripes, erased, status, corrected, stream);
+    const size_t n = static_cast<size_t>(c->n);
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (corrected) std::fill(corrected, corrected + stripes * n, 0u);
+    if (c->m == 0 || cp.live.empty()) return RS_OK;  // no parity: every stripe is a codeword | no stripe has any bytes
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return correct_columns_lens(c, *sc.L, stripes, cp.degraded ? erased : nullptr, lens, cp, first, shard_ptrs, status,
+                                corrected, static_cast<hipStream_t>(stream));
 }
 
 int rs_encode(rs_ctx* c, const uint8_t* input, size_t len, uint8_t* parity) {

@@ -40,7 +40,7 @@ EXPORTS = (
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_ptrs", "rs_correct_columns_ptrs",
     "rs_reconstruct_checked", "rs_reconstruct_checked_ptrs",
-    "rs_verify_ptrs_lens", "rs_reconstruct_checked_ptrs_lens",
+    "rs_verify_ptrs_lens", "rs_reconstruct_checked_ptrs_lens", "rs_correct_columns_ptrs_lens",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
     "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
@@ -178,6 +178,7 @@ def _lib() -> ctypes.CDLL:
             "rs_reconstruct_checked_ptrs": (i32, [vp, vp, sz, sz, vp, vp, vp]),
             "rs_verify_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, vp, vp]),
             "rs_reconstruct_checked_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, vp, vp]),
+            "rs_correct_columns_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
             "rs_combine_lens": (i32, [vp, ctypes.POINTER(CombineJob), sz, ctypes.POINTER(sz), vp]),
@@ -352,7 +353,9 @@ class FEC:
         update (7), column scrub (8) or combine_lens of mixed lengths (9);
         10 to 13 the pointer-mode check and column kernels and the repair
         kernels, 14 to 16 the per-stripe-length twins of verify, check and
-        repair (verify_ptrs_lens, reconstruct_checked_ptrs_lens): diagnostics."""
+        repair (verify_ptrs_lens, reconstruct_checked_ptrs_lens), 17 the
+        per-job-length twin of the pointer-mode column kernel
+        (correct_columns_ptrs_lens): diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -806,6 +809,30 @@ class FEC:
             _check(rc, "rs_correct_columns_ptrs")
         return [st[s] for s in range(stripes)], cnt[:stripes * self.n]
 
+    def correct_columns_ptrs_lens(self, shard_ptrs_dev: int, shard_lens: Sequence[int], stripes: int,
+                                  erased: Optional[bytes] = None, stream: int = 0):
+        """rs_correct_columns_ptrs_lens: correct_columns_ptrs where stripe s
+        has shard_lens[s] bytes per shard (as verify_ptrs_lens takes them).
+        Bytes at or beyond a stripe's length are neither decoded nor written;
+        a stripe of length 0 ends RS_OK with zero counts.  Returns (status,
+        corrected) as correct_columns_ptrs; raises only for argument, device
+        or memory errors and for more than m erasures."""
+        import numpy as np
+        lens = self._stripe_lens(shard_lens, stripes)
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        st = (ctypes.c_int * max(stripes, 1))()
+        cnt = np.zeros(max(stripes * self.n, 1), dtype=np.uint32)
+        rc = _lib().rs_correct_columns_ptrs_lens(self._h, shard_ptrs_dev or None, lens, stripes,
+                                                 ctypes.cast(buf, ctypes.c_void_p), st,
+                                                 ctypes.c_void_p(cnt.ctypes.data), stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_columns_ptrs_lens")
+        return [st[s] for s in range(stripes)], cnt[:stripes * self.n]
+
     def pattern_count(self) -> int:
         return _lib().rs_pattern_count(self._h)
 
@@ -815,7 +842,8 @@ class FEC:
      STAT_UPDATE_COPY_COMMITS, STAT_READ_REGENERATED, STAT_READ_COPIED, STAT_CHECK_STRIPES,
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
      STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES, STAT_BATCH_LENS_PASSES,
-     STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED, STAT_SCRUB_LENS_LAUNCHES) = range(28)
+     STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED, STAT_SCRUB_LENS_LAUNCHES,
+     STAT_COLUMN_LENS_LAUNCHES) = range(29)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
