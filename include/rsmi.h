@@ -94,7 +94,9 @@ const char *rs_strerror(int status);
  * "verify_K10_MG4_B256_lens", "check_K10_MG4_B256_ptrs_lens" and
  * "repair_K10_MG4_B256_ptrs_lens"; which = 17: the per-job-length twin of
  * which = 11 that serves rs_correct_columns_ptrs_lens calls of mixed lengths,
- * e.g. "columns_MG4_B256_ptrs_lens" ("none" for m > 16). */
+ * e.g. "columns_MG4_B256_ptrs_lens" ("none" for m > 16); which = 18 and 19:
+ * the sector-checksum kernel of the rs_crc32c_* calls and its pointer-mode
+ * twin, "crc32c_H16_B256" and "crc32c_H16_B256_ptrs". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -785,6 +787,117 @@ int rs_correct_columns_ptrs_lens(rs_ctx *ctx, const uint64_t *shard_ptrs, const 
                                  uint32_t *corrected /* HOST uint32[stripes*n], may be NULL */,
                                  void *stream);
 
+/* ---- sector checksums: CRC-32C of stored shards ----------------------------
+ * Every scrub above asks whether the stored shards lie on a codeword.  These
+ * calls ask what a store has to ask first -- are these the bytes that were
+ * written? -- with a checksum per sector that is kept apart from the data.  A
+ * mismatch LOCATES the damage, so errors become erasures: rs_correct_crc32c
+ * repairs up to m wrong shards per stripe where the codeword scrubs repair
+ * floor(m / 2), never lands on a wrong codeword, and catches what no codeword
+ * check can: a valid codeword of the wrong data (a stale shard set, a lost
+ * update).
+ *
+ * The checksum is CRC-32C (Castagnoli) exactly as iSCSI / RFC 3720 defines it:
+ * reflected polynomial 0x82F63B78, initial value 0xFFFFFFFF, final XOR
+ * 0xFFFFFFFF, stored as a host-order uint32_t ("123456789" -> 0xE3069283, the
+ * empty message -> 0).  A shard of shard_len bytes has nsec = ceil(shard_len /
+ * sector_len) sectors; the checksum of sector j covers the bytes [j *
+ * sector_len, min((j + 1) * sector_len, shard_len)) and nothing else -- never
+ * the padding up to 16 or the pitch gap -- so a host reproduces it from the
+ * shard's contents alone (rs_crc32c_host).  sector_len is a power of two,
+ * 512 <= sector_len <= 65536.
+ *
+ * Layout and alignment rules are those of rs_encode_stripes.  erased is a HOST
+ * array of stripes * n flags as for rs_reconstruct_stripes, not retained; it
+ * may be NULL (nothing missing) in every one of these calls.  The slots
+ * of erased shards are never dereferenced, and in the pointer calls their
+ * table entries are not loaded.  crcs is a DEVICE array of uint32_t, 4-byte
+ * aligned: sector j of shard i of stripe s is crcs[(s * n + i) * crc_pitch +
+ * j], crc_pitch >= nsec; entries between nsec and crc_pitch are never read or
+ * written.  A slice call -- data and parity advanced by a multiple of
+ * sector_len, crcs by the same number of sectors, shard_len shortened -- works
+ * on a store's full table directly, as the slice forms of update and read do;
+ * sector indices are then relative to the slice.  That is also the recipe for
+ * sector-granular regeneration, which these calls do not do themselves: check,
+ * then rs_read_stripes the slice that covers the bad sectors into place.
+ *
+ * rs_crc32c_stripes computes and stores the checksums of every present shard;
+ * the entries of erased shards are left as they are.  Reads data and parity
+ * only.  Enqueued on stream; returns when queued.
+ *
+ * rs_crc32c_check_stripes compares instead: first_bad (DEVICE,
+ * uint32[stripes * n], 4-byte aligned) gets, at [s * n + i], the lowest sector
+ * index of shard i of stripe s whose bytes do not match the stored checksum,
+ * or RS_VERIFY_CLEAN; an erased shard gets RS_VERIFY_CLEAN.  Writes nothing
+ * but first_bad.  Enqueued.  Copied to the host and reduced to non-zero / zero
+ * (clean), it is an `erased` array for rs_reconstruct_stripes /
+ * rs_reconstruct_checked.
+ *
+ * rs_crc32c_ptrs / rs_crc32c_check_ptrs are the same two calls for the pointer
+ * placement of rs_reconstruct_ptrs (shard_ptrs: DEVICE, [stripes][n], 8-byte
+ * aligned, 16-byte-aligned addresses, only read).
+ *
+ * rs_correct_crc32c is the repair, synchronous and shaped like
+ * rs_correct_degraded:
+ *  1. every present shard is checked; B(s) is the set of present shards of
+ *     stripe s with a mismatching sector, X(s) its erased shards;
+ *  2. B empty: the stripe is RS_OK and untouched (a clean stripe with more
+ *     than m erasures too);
+ *  3. |X + B| > m: the stripe is RS_ETOO_MANY_ERRORS and nothing in it is
+ *     written;
+ *  4. otherwise every shard of B is regenerated in place, whole, from the k
+ *     survivors Rebuild chooses for X + B (the read path of rs_read_stripes:
+ *     flags X + B, wanted B, every destination the shard's own slot; the slots
+ *     of X are neither read nor written), all stripes in one batched launch;
+ *  5. the regenerated shards are checked against their stored checksums again,
+ *     in one launch over those shards only; one that still mismatches makes its
+ *     stripe RS_ETOO_MANY_ERRORS: either its stored checksum is wrong, or a
+ *     survivor is wrong under a matching checksum.
+ * status (HOST int[stripes], may be NULL) and rewritten (HOST
+ * uint8_t[stripes * n], may be NULL) as for rs_correct_degraded: rewritten is
+ * non-zero for regenerated shards, never for erased ones.  Returns RS_OK if
+ * every stripe ends with all present shards matching, else
+ * RS_ETOO_MANY_ERRORS.  RS_ENOT_ENOUGH, with nothing written, when a stripe
+ * with more than m erasures also has a mismatch.  Checksums are never written
+ * by this call, and it does not ask whether a stripe is a codeword:
+ * rs_verify_degraded answers that.  With m == 0 any mismatch is
+ * RS_ETOO_MANY_ERRORS.
+ *
+ * All or nothing, before anything is launched: RS_EINVAL for a NULL ctx (before
+ * any HIP call), NULL or misaligned crcs or first_bad, a sector_len that is not
+ * a power of two in range, crc_pitch < nsec, stripes * n >= 2^32, more than
+ * 2^31 - 1 blocks (a block is 64 KiB of a shard, or four sectors if that is
+ * more), and whatever rs_verify_stripes / rs_verify_ptrs refuses.  stripes == 0
+ * or shard_len == 0: RS_OK, nothing launched.  Device sets route by pointer as
+ * rs_verify_stripes does.  RS_STAT_CRC_SECTORS counts the sectors checksummed
+ * by any launch of these calls (the second check of rs_correct_crc32c
+ * included), RS_STAT_CRC_REGENERATED the shards rs_correct_crc32c regenerated.
+ * rs_kernel_name which = 18 and 19 name the kernel and its pointer twin. */
+int rs_crc32c_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride, const void *parity,
+                      size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len, size_t stripes,
+                      const uint8_t *erased /* HOST, may be NULL */, size_t sector_len, uint32_t *crcs,
+                      size_t crc_pitch, void *stream);
+int rs_crc32c_check_stripes(rs_ctx *ctx, const void *data, size_t data_stripe_stride, const void *parity,
+                            size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len, size_t stripes,
+                            const uint8_t *erased /* HOST, may be NULL */, size_t sector_len,
+                            const uint32_t *crcs, size_t crc_pitch, uint32_t *first_bad, void *stream);
+int rs_crc32c_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
+                   const uint8_t *erased /* HOST, may be NULL */, size_t sector_len, uint32_t *crcs,
+                   size_t crc_pitch, void *stream);
+int rs_crc32c_check_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
+                         const uint8_t *erased /* HOST, may be NULL */, size_t sector_len, const uint32_t *crcs,
+                         size_t crc_pitch, uint32_t *first_bad, void *stream);
+int rs_correct_crc32c(rs_ctx *ctx, void *data, size_t data_stripe_stride, void *parity,
+                      size_t parity_stripe_stride, size_t shard_pitch, size_t shard_len, size_t stripes,
+                      const uint8_t *erased /* HOST, may be NULL */, size_t sector_len, const uint32_t *crcs,
+                      size_t crc_pitch, int *status /* HOST int[stripes], may be NULL */,
+                      uint8_t *rewritten /* HOST uint8_t[stripes*n], may be NULL */, void *stream);
+/* rs_crc32c_host: the host reference (slice-by-8): out[i] = CRC-32C of the
+ * lens[i] bytes at bufs[i].  Needs no context and no GPU.  count == 0: RS_OK;
+ * RS_EINVAL for count < 0, a NULL array with count > 0, or a NULL buffer of
+ * non-zero length. */
+int rs_crc32c_host(int count, const uint8_t *const *bufs, const size_t *lens, uint32_t *out);
+
 /* Cached decode patterns held by the ctx (diagnostics / tests).  The cache
  * holds at most 2^20 patterns (RSMI_PATTERN_CAP); a call that would exceed
  * that evicts it whole, with no host synchronisation (the rebuilt rows wait
@@ -824,6 +937,8 @@ enum {
     RS_STAT_REPAIR_CHECKED = 26,   /* stripes repaired and checked by the repair kernel (rs_reconstruct_checked*) */
     RS_STAT_SCRUB_LENS_LAUNCHES = 27, /* rs_verify_ptrs_lens / rs_reconstruct_checked_ptrs_lens calls served by the per-stripe-length kernels */
     RS_STAT_COLUMN_LENS_LAUNCHES = 28, /* column launches of rs_correct_columns_ptrs_lens served by the per-job-length twin (not by rs_correct_columns_ptrs') */
+    RS_STAT_CRC_SECTORS = 29,      /* sectors checksummed by the rs_crc32c_* calls and rs_correct_crc32c */
+    RS_STAT_CRC_REGENERATED = 30,  /* shards regenerated by rs_correct_crc32c          */
 };
 int64_t rs_stat(const rs_ctx *ctx, int which);
 
@@ -937,6 +1052,7 @@ int rs_stream_sync(rs_ctx *ctx, void *stream);
  *    rs_verify_degraded, rs_correct_degraded, rs_correct_columns, rs_update_degraded, rs_reconstruct_ptrs,
  *    rs_verify_ptrs, rs_correct_columns_ptrs, rs_reconstruct_checked, rs_reconstruct_checked_ptrs,
  *    rs_verify_ptrs_lens, rs_reconstruct_checked_ptrs_lens, rs_correct_columns_ptrs_lens,
+ *    rs_crc32c_stripes, rs_crc32c_check_stripes, rs_crc32c_ptrs, rs_crc32c_check_ptrs, rs_correct_crc32c,
  *    rs_fill_splitmix, rs_blake2b_device) run on a member on the device that holds their (first) device buffer, RS_EINVAL
  *    if no member is on it; rs_prepare_patterns (stream must be NULL) runs
  *    on every member; rs_blake2b* on the least-busy member;

@@ -34,6 +34,7 @@
 #include "column_correct.hpp"
 #include "column_decode.hpp"
 #include "column_lens_plan.hpp"
+#include "crc32c.hpp"
 #include "combine_plan.hpp"
 #include "device_set.hpp"
 #include "gf256.hpp"
@@ -382,6 +383,7 @@ struct rs_ctx {
     std::atomic<int64_t> combine_lens_launches{0};                       // rs_combine_lens calls the per-job-length kernel served
     std::atomic<int64_t> update_degraded{0}, update_absorbed{0};         // rs_update_degraded (rs_stat)
     std::atomic<int64_t> column_stripes{0}, column_bytes{0};             // rs_correct_columns (rs_stat)
+    std::atomic<int64_t> crc_sectors{0}, crc_regenerated{0};             // rs_crc32c_* / rs_correct_crc32c (rs_stat)
     bool repair_fused = true;   // rs_reconstruct_checked: the repair kernel; false: the check and reconstruct launches (RSMI_REPAIR_FUSED=0)
     uint32_t xcd_repair = 0;    // repair kernel: blocks per XCD region (0: natural order, ~0u: a stripe; RSMI_XCD_REPAIR_REGION)
     uint32_t xcd_update = ~0u;  // update kernel: blocks per XCD region (~0u: a stripe; RSMI_XCD_UPD_REGION)
@@ -1337,7 +1339,7 @@ rsmi::ReadArgs read_args(const rs_ctx* c, const StripeView& v, size_t njobs) {
 }
 
 // Whose counters a read launch feeds.
-enum class ReadFor { kRead, kScrub, kUpdate };
+enum class ReadFor { kRead, kScrub, kUpdate, kCrc };
 
 // Launches a planned rs_read_stripes on stream s.  With jobs, pat_mu is held
 // (shared or exclusive) and L.pid holds the built pattern of every job.  The
@@ -1380,6 +1382,8 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::Re
                                      static_cast<uint32_t>(ncopy), v.span(), s);
     if (e == hipSuccess && who == ReadFor::kScrub) {
         c->scrub_regenerated += static_cast<int64_t>(count);
+    } else if (e == hipSuccess && who == ReadFor::kCrc) {
+        c->crc_regenerated += static_cast<int64_t>(count);
     } else if (e == hipSuccess && who == ReadFor::kRead) {
         c->read_regenerated += static_cast<int64_t>(count);
         c->read_copied += static_cast<int64_t>(ncopy);
@@ -1390,8 +1394,8 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::Re
 // rs_read_stripes on stream s with lease L: the patterns of the jobs' stripes
 // come from the cache rs_reconstruct_stripes fills (with_patterns; a plan
 // without jobs -- copies only -- takes no lock).  who: the call regenerates
-// located shards for rs_correct_degraded (kScrub), which counts them in a
-// counter of its own, or old contents for rs_update_degraded (kUpdate), which
+// located shards for rs_correct_degraded (kScrub) or rs_correct_crc32c (kCrc),
+// which count them in counters of their own, or old contents for rs_update_degraded (kUpdate), which
 // counts none.
 int read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a,
                  hipStream_t s, ReadFor who = ReadFor::kRead) {
@@ -3459,6 +3463,8 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 15) return rsmi::check_lens_variant_name(c->k);
     if (which == 16) return rsmi::repair_lens_variant_name(c->k);
     if (which == 17) return rsmi::column_lens_variant_name(c->m);
+    if (which == 18) return rsmi::crc32c_variant_name();
+    if (which == 19) return rsmi::crc32c_ptrs_variant_name();
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3526,6 +3532,8 @@ int64_t rs_stat(const rs_ctx* c, int which) {
         case RS_STAT_REPAIR_CHECKED: return c->repair_checked.load();
         case RS_STAT_SCRUB_LENS_LAUNCHES: return c->scrub_lens_launches.load();
         case RS_STAT_COLUMN_LENS_LAUNCHES: return c->column_lens_launches.load();
+        case RS_STAT_CRC_SECTORS: return c->crc_sectors.load();
+        case RS_STAT_CRC_REGENERATED: return c->crc_regenerated.load();
         case RS_STAT_LEASES: {
             std::lock_guard<std::mutex> lk(const_cast<rs_ctx*>(c)->lease_mu);
             return static_cast<int64_t>(c->leases.size());
@@ -4045,6 +4053,247 @@ int rs_correct_columns_ptrs_lens(rs_ctx* c, const uint64_t* shard_ptrs, const si
     if (sc.error() != RS_OK) return sc.error();
     return correct_columns_lens(c, *sc.L, stripes, cp.degraded ? erased : nullptr, lens, cp, first, shard_ptrs, status,
                                 corrected, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------ sector checksums ----
+namespace {
+// The argument checks the rs_crc32c calls share, behind the NULL-ctx and the
+// nothing-to-do checks: every refusal before anything is launched.  ptrs: the
+// call is one of the pointer placement (v = StripeView::ptrs), whose table
+// shard_ptrs may be NULL or misaligned and is refused here; otherwise
+// shard_ptrs is nullptr.  Routes c to the member that holds the shards and
+// fills in the kernel's arguments and plan for all stripes * n shards.
+int crc_args(rs_ctx*& c, const StripeView& v, const uint64_t* shard_ptrs, bool ptrs, size_t stripes, size_t sector_len,
+             const uint32_t* crcs, size_t crc_pitch, const uint32_t* first_bad, bool check, rsmi::CrcArgs* a) {
+    if (!crcs || (reinterpret_cast<uintptr_t>(crcs) & 3u)) return RS_EINVAL;
+    if (check && (!first_bad || (reinterpret_cast<uintptr_t>(first_bad) & 3u))) return RS_EINVAL;
+    if (!rsmi::crc32c_sector_len_ok(sector_len)) return RS_EINVAL;
+    if (crc_pitch < (v.len + sector_len - 1) / sector_len) return RS_EINVAL;
+    if (stripes > 0xFFFFFFFFull / static_cast<size_t>(c->n)) return RS_EINVAL;  // 32-bit shard indices
+    if (ptrs) {
+        if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return RS_EINVAL;
+        if (v.span() / 16 >= (size_t(1) << 28)) return RS_EINVAL;  // as rs_verify_ptrs
+    } else if (!check_stripes_args(c, v)) {
+        return RS_EINVAL;
+    }
+    if (!route(c, ptrs ? static_cast<const void*>(shard_ptrs) : v.data)) return RS_EINVAL;
+    *a = rsmi::CrcArgs{};
+    a->data = static_cast<const uint8_t*>(v.data);
+    a->parity = static_cast<const uint8_t*>(v.parity);
+    a->data_ss = v.dss;
+    a->parity_ss = v.pss;
+    a->pitch = v.pitch;
+    a->shard_ptrs = shard_ptrs;
+    a->k = static_cast<uint32_t>(c->k);
+    a->n = static_cast<uint32_t>(c->n);
+    a->crcs = const_cast<uint32_t*>(crcs);
+    a->crc_pitch = crc_pitch;
+    a->first_bad = const_cast<uint32_t*>(first_bad);
+    a->nshards = stripes * static_cast<size_t>(c->n);
+    return rsmi::plan_crc32c(a, v.len, sector_len) ? RS_OK : RS_EINVAL;
+}
+
+// The present shards' indices s * n + i of a call with erasure flags; false
+// (and no list) when no flag is set.
+bool present_shards(const uint8_t* erased, size_t total, std::vector<uint32_t>* list) {
+    list->clear();
+    if (!erased || !std::any_of(erased, erased + total, [](uint8_t f) { return f != 0; })) return false;
+    for (size_t x = 0; x < total; ++x)
+        if (!erased[x]) list->push_back(static_cast<uint32_t>(x));
+    return true;
+}
+
+// One launch of the checksum kernel on stream s: over the shards of `list`
+// (host; through lease L's table upload) or, with list == nullptr, over all
+// a.nshards of them (no lease).  A check first presets all `total` entries
+// of a.first_bad to RS_VERIFY_CLEAN.
+int crc_launch(rs_ctx* c, Lease* L, rsmi::CrcArgs a, const std::vector<uint32_t>* list, size_t total, bool check,
+               hipStream_t s) {
+    if (check && hipMemsetAsync(a.first_bad, 0xFF, total * sizeof(uint32_t), s) != hipSuccess) return RS_EDEVICE;
+    if (!list) {
+        const int rc = hip_status(rsmi::launch_crc32c(a, check, s));
+        if (rc == RS_OK) c->crc_sectors += static_cast<int64_t>(a.nshards * a.nsec);
+        return rc;
+    }
+    const size_t count = list->size();
+    if (count == 0) return RS_OK;  // every shard is missing
+    Tables t;
+    const int up = upload_tables(c, *L, 0, count * sizeof(uint32_t), s, &t,
+                                 [&](uint8_t* hb) { std::memcpy(hb, list->data(), count * sizeof(uint32_t)); });
+    if (up != RS_OK) return up;
+    a.shards = reinterpret_cast<const uint32_t*>(t.dev);
+    a.nshards = count;
+    const int rc = hip_status(rsmi::launch_crc32c(a, check, s));
+    if (rc == RS_OK) c->crc_sectors += static_cast<int64_t>(count * a.nsec);
+    return finish_launch(c, *L, s, false, rc);
+}
+
+// The four enqueued calls behind their NULL-ctx and nothing-to-do checks.
+int crc_call(rs_ctx* c, const StripeView& v, const uint64_t* shard_ptrs, bool ptrs, size_t stripes,
+             const uint8_t* erased, size_t sector_len, const uint32_t* crcs, size_t crc_pitch, uint32_t* first_bad,
+             bool check, hipStream_t s) {
+    rsmi::CrcArgs a;
+    const int rc = crc_args(c, v, shard_ptrs, ptrs, stripes, sector_len, crcs, crc_pitch, first_bad, check, &a);
+    if (rc != RS_OK) return rc;
+    const size_t total = stripes * static_cast<size_t>(c->n);
+    std::vector<uint32_t> present;
+    // No flag set: one launch, without a lock or a lease.
+    if (!present_shards(erased, total, &present)) {
+        DeviceGuard g(c->device);
+        if (!g.ok) return RS_EDEVICE;
+        return crc_launch(c, nullptr, a, nullptr, total, check, s);
+    }
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return crc_launch(c, sc.L, a, &present, total, check, s);
+}
+
+// rs_correct_crc32c on stream s with lease L, behind its argument checks (a:
+// the planned check of all shards).  Device workspace (L.d_scrub) and its
+// pinned mirror (L.st_scrub): first_bad u32 [stripes * n].  Check of the
+// present shards, verdicts to the host; the located shards B of every stripe
+// with |X + B| <= m regenerated in place by the read path with the flags
+// X + B, wanted B and every dst the shard's own slot (as scrub_stripes does),
+// in one batched launch; then the check of the regenerated shards alone.
+int correct_crc32c(rs_ctx* c, Lease& L, const StripeView& v, rsmi::CrcArgs a, size_t stripes, const uint8_t* erased,
+                   int* status, uint8_t* rewritten, hipStream_t s) {
+    const size_t n = static_cast<size_t>(c->n), total = stripes * n;
+    L.begin(s);
+    if (!L.st_scrub.acquire(total * sizeof(uint32_t)) || !L.d_scrub.reserve_on(total * sizeof(uint32_t), s))
+        return RS_ENOMEM;
+    uint32_t* const h_fb = static_cast<uint32_t*>(L.st_scrub.p);
+    a.first_bad = static_cast<uint32_t*>(L.d_scrub.p);
+    // Every exit records the lease's last device use.
+    struct End {
+        Lease& L;
+        hipStream_t s;
+        ~End() { L.end(s); }
+    } end_guard{L, s};
+    // A check of the listed shards (all of them: list == nullptr) and the
+    // verdicts to the host.
+    auto check = [&](const std::vector<uint32_t>* list) -> int {
+        const int rc = crc_launch(c, &L, a, list, total, true, s);
+        if (rc != RS_OK) return rc;
+        if (hipMemcpyAsync(h_fb, a.first_bad, total * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return RS_EDEVICE;
+        return RS_OK;
+    };
+    std::vector<uint32_t> list;
+    const bool degraded = present_shards(erased, total, &list);
+    int rc = check(degraded ? &list : nullptr);
+    if (rc != RS_OK) return rc;
+
+    // known: X + B of the stripes that are repaired, nothing for the others.
+    std::vector<uint8_t> known(total, 0);
+    std::vector<rs_shard_read> reads;
+    std::vector<uint32_t> live;  // the stripes that are repaired
+    bool failed = false;
+    auto give_up = [&](size_t i) {
+        if (status) status[i] = RS_ETOO_MANY_ERRORS;
+        failed = true;
+    };
+    for (int pass = 0; pass < 2; ++pass) {  // 0: the refusal, before anything is written
+        for (size_t i = 0; i < stripes; ++i) {
+            int e = 0, b = 0;
+            for (size_t id = 0; id < n; ++id) {
+                e += degraded && erased[i * n + id] != 0;
+                b += h_fb[i * n + id] != RS_VERIFY_CLEAN;
+            }
+            if (b == 0) continue;
+            if (pass == 0) {
+                if (e > c->m) return RS_ENOT_ENOUGH;
+                continue;
+            }
+            if (e + b > c->m) {
+                give_up(i);
+                continue;
+            }
+            for (size_t id = 0; id < n; ++id) {
+                const bool bad = h_fb[i * n + id] != RS_VERIFY_CLEAN;
+                known[i * n + id] = bad || (degraded && erased[i * n + id] != 0) ? 1 : 0;
+                if (bad)
+                    reads.push_back(rs_shard_read{i, static_cast<uint32_t>(id), 0u,
+                                                  reinterpret_cast<void*>(v.slot(i, id, c->k))});
+            }
+            live.push_back(static_cast<uint32_t>(i));
+        }
+    }
+    if (reads.empty()) return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+    rsmi::ReadPlan rp;
+    rc = rsmi::plan_reads(c->k, c->n, stripes, known.data(), v.span(), reads.data(), reads.size(), &rp);
+    if (rc != RS_OK) return rc;
+    rsmi::ReadArgs ra = read_args(c, v, rp.jobs.size());
+    if (!rsmi::plan_read(&ra, rp.max_j)) return RS_EINVAL;
+    rc = read_stripes(c, L, v, rp, ra, s, ReadFor::kCrc);
+    if (rc != RS_OK) return rc;
+    list.clear();
+    for (const rs_shard_read& r : reads) {
+        const size_t x = r.stripe * n + r.shard;
+        if (rewritten) rewritten[x] = 1;
+        list.push_back(static_cast<uint32_t>(x));
+    }
+    // The regenerated shards against their stored checksums.
+    rc = check(&list);
+    if (rc != RS_OK) return rc;
+    for (uint32_t i : live)
+        for (size_t x = i * n; x < (i + 1) * n; ++x)
+            if (h_fb[x] != RS_VERIFY_CLEAN) {
+                give_up(i);
+                break;
+            }
+    return failed ? RS_ETOO_MANY_ERRORS : RS_OK;
+}
+}  // namespace
+
+int rs_crc32c_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch, size_t len,
+                      size_t stripes, const uint8_t* erased, size_t sector_len, uint32_t* crcs, size_t crc_pitch,
+                      void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    return crc_call(c, StripeView::of(data, dss, parity, pss, pitch, len), nullptr, false, stripes, erased, sector_len,
+                    crcs, crc_pitch, nullptr, false, static_cast<hipStream_t>(stream));
+}
+
+int rs_crc32c_check_stripes(rs_ctx* c, const void* data, size_t dss, const void* parity, size_t pss, size_t pitch,
+                            size_t len, size_t stripes, const uint8_t* erased, size_t sector_len, const uint32_t* crcs,
+                            size_t crc_pitch, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    return crc_call(c, StripeView::of(data, dss, parity, pss, pitch, len), nullptr, false, stripes, erased, sector_len,
+                    crcs, crc_pitch, first_bad, true, static_cast<hipStream_t>(stream));
+}
+
+int rs_crc32c_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
+                   size_t sector_len, uint32_t* crcs, size_t crc_pitch, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    return crc_call(c, StripeView::ptrs(round_up(len, 16), len), shard_ptrs, true, stripes, erased, sector_len, crcs,
+                    crc_pitch, nullptr, false, static_cast<hipStream_t>(stream));
+}
+
+int rs_crc32c_check_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,
+                         size_t sector_len, const uint32_t* crcs, size_t crc_pitch, uint32_t* first_bad, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    return crc_call(c, StripeView::ptrs(round_up(len, 16), len), shard_ptrs, true, stripes, erased, sector_len, crcs,
+                    crc_pitch, first_bad, true, static_cast<hipStream_t>(stream));
+}
+
+int rs_correct_crc32c(rs_ctx* c, void* data, size_t dss, void* parity, size_t pss, size_t pitch, size_t len,
+                      size_t stripes, const uint8_t* erased, size_t sector_len, const uint32_t* crcs, size_t crc_pitch,
+                      int* status, uint8_t* rewritten, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (stripes == 0 || len == 0) return RS_OK;
+    const StripeView v = StripeView::of(data, dss, parity, pss, pitch, len);
+    rsmi::CrcArgs a;
+    const int rc = crc_args(c, v, nullptr, false, stripes, sector_len, crcs, crc_pitch, nullptr, false, &a);
+    if (rc != RS_OK) return rc;
+    if (status) std::fill(status, status + stripes, static_cast<int>(RS_OK));
+    if (rewritten) std::memset(rewritten, 0, stripes * static_cast<size_t>(c->n));
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return correct_crc32c(c, *sc.L, v, a, stripes, erased, status, rewritten, static_cast<hipStream_t>(stream));
 }
 
 int rs_encode(rs_ctx* c, const uint8_t* input, size_t len, uint8_t* parity) {

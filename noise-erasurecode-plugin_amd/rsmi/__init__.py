@@ -44,6 +44,8 @@ EXPORTS = (
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
     "rs_verify_degraded", "rs_correct_degraded", "rs_correct_columns", "rs_update_degraded", "rs_combine",
     "rs_combine_lens", "rs_encode_batch_lens", "rs_decode_batch_lens",
+    "rs_crc32c_stripes", "rs_crc32c_check_stripes", "rs_crc32c_ptrs", "rs_crc32c_check_ptrs",
+    "rs_correct_crc32c", "rs_crc32c_host",
     "rs_pattern_survivors",
     "rs_pattern_evictions",
     "rs_prepare_patterns",
@@ -180,6 +182,12 @@ def _lib() -> ctypes.CDLL:
             "rs_reconstruct_checked_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, vp, vp]),
             "rs_correct_columns_ptrs_lens": (i32, [vp, vp, ctypes.POINTER(sz), sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_correct_columns": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
+            "rs_crc32c_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, sz, vp, sz, vp]),
+            "rs_crc32c_check_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, sz, vp, sz, vp, vp]),
+            "rs_crc32c_ptrs": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, vp]),
+            "rs_crc32c_check_ptrs": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, vp, vp]),
+            "rs_correct_crc32c": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, sz, vp, sz, ctypes.POINTER(i32), vp, vp]),
+            "rs_crc32c_host": (i32, [i32, ctypes.POINTER(vp), ctypes.POINTER(sz), vp]),
             "rs_combine": (i32, [vp, ctypes.POINTER(CombineJob), sz, sz, vp]),
             "rs_combine_lens": (i32, [vp, ctypes.POINTER(CombineJob), sz, ctypes.POINTER(sz), vp]),
             "rs_pattern_survivors": (i32, [vp, vp, ctypes.POINTER(i32)]),
@@ -355,7 +363,8 @@ class FEC:
         kernels, 14 to 16 the per-stripe-length twins of verify, check and
         repair (verify_ptrs_lens, reconstruct_checked_ptrs_lens), 17 the
         per-job-length twin of the pointer-mode column kernel
-        (correct_columns_ptrs_lens): diagnostics."""
+        (correct_columns_ptrs_lens), 18 and 19 the sector-checksum kernel
+        (crc32c_*) and its pointer-mode twin: diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -603,6 +612,83 @@ class FEC:
             _check(rc, "rs_correct_degraded")
         return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
 
+    # -- sector checksums (CRC-32C of stored shards) -----------------------------
+    def _flags(self, erased: Optional[bytes], stripes: int):
+        if erased is None:
+            return None
+        if len(erased) != stripes * self.n:
+            raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+        return ctypes.c_char_p(bytes(erased))
+
+    def crc32c_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                       pitch: int, shard_len: int, stripes: int, sector_len: int, crcs_ptr: int,
+                       crc_pitch: int, erased: Optional[bytes] = None, stream: int = 0) -> None:
+        """rs_crc32c_stripes: the CRC-32C of sector j of shard i of stripe s
+        goes to the device uint32 array crcs_ptr[(s * n + i) * crc_pitch + j];
+        a sector covers sector_len bytes, the last one what is left below
+        shard_len.  Entries of erased shards (erased: stripes * n flags, or
+        None) are left as they are.  Enqueued on stream."""
+        buf = self._flags(erased, stripes)
+        _check(_lib().rs_crc32c_stripes(self._h, data_ptr, data_stride, parity_ptr, parity_stride, pitch,
+                                        shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), sector_len,
+                                        crcs_ptr or None, crc_pitch, stream or None), "rs_crc32c_stripes")
+
+    def crc32c_check_stripes(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                             pitch: int, shard_len: int, stripes: int, sector_len: int, crcs_ptr: int,
+                             crc_pitch: int, first_bad_ptr: int, erased: Optional[bytes] = None,
+                             stream: int = 0) -> None:
+        """rs_crc32c_check_stripes: first_bad_ptr is a device array of
+        stripes * n uint32; entry s * n + i receives the lowest sector of
+        shard i of stripe s that does not match its stored checksum, or
+        RS_VERIFY_CLEAN (also for erased shards).  Enqueued on stream."""
+        buf = self._flags(erased, stripes)
+        _check(_lib().rs_crc32c_check_stripes(self._h, data_ptr, data_stride, parity_ptr, parity_stride, pitch,
+                                              shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), sector_len,
+                                              crcs_ptr or None, crc_pitch, first_bad_ptr or None, stream or None),
+               "rs_crc32c_check_stripes")
+
+    def crc32c_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, sector_len: int, crcs_ptr: int,
+                    crc_pitch: int, erased: Optional[bytes] = None, stream: int = 0) -> None:
+        """rs_crc32c_ptrs: crc32c_stripes for shards at the device addresses
+        in the device array shard_ptrs_dev[s * n + i]; entries of erased
+        shards are not loaded.  Enqueued on stream."""
+        buf = self._flags(erased, stripes)
+        _check(_lib().rs_crc32c_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
+                                     ctypes.cast(buf, ctypes.c_void_p), sector_len, crcs_ptr or None, crc_pitch,
+                                     stream or None), "rs_crc32c_ptrs")
+
+    def crc32c_check_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, sector_len: int, crcs_ptr: int,
+                          crc_pitch: int, first_bad_ptr: int, erased: Optional[bytes] = None,
+                          stream: int = 0) -> None:
+        """rs_crc32c_check_ptrs: crc32c_check_stripes on the pointer
+        placement.  Enqueued on stream."""
+        buf = self._flags(erased, stripes)
+        _check(_lib().rs_crc32c_check_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
+                                           ctypes.cast(buf, ctypes.c_void_p), sector_len, crcs_ptr or None,
+                                           crc_pitch, first_bad_ptr or None, stream or None),
+               "rs_crc32c_check_ptrs")
+
+    def correct_crc32c(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
+                       pitch: int, shard_len: int, stripes: int, sector_len: int, crcs_ptr: int,
+                       crc_pitch: int, erased: Optional[bytes] = None, stream: int = 0):
+        """rs_correct_crc32c (repair by checksum): (status, rewritten) as
+        correct_degraded.  Every present shard with a sector that does not
+        match its stored checksum is regenerated in place, up to m of them
+        per stripe together with the erased ones, and checked again; the
+        checksums themselves are never written.  Raises only for argument,
+        device or memory errors and for a damaged stripe with more than m
+        erasures."""
+        buf = self._flags(erased, stripes)
+        st = (ctypes.c_int * max(stripes, 1))()
+        rw = ctypes.create_string_buffer(max(stripes * self.n, 1))
+        rc = _lib().rs_correct_crc32c(self._h, data_ptr, data_stride, parity_ptr, parity_stride, pitch,
+                                      shard_len, stripes, ctypes.cast(buf, ctypes.c_void_p), sector_len,
+                                      crcs_ptr or None, crc_pitch, st, ctypes.cast(rw, ctypes.c_void_p),
+                                      stream or None)
+        if rc != RS_ETOO_MANY_ERRORS:
+            _check(rc, "rs_correct_crc32c")
+        return [st[s] for s in range(stripes)], rw.raw[:stripes * self.n]
+
     def correct_columns(self, data_ptr: int, data_stride: int, parity_ptr: int, parity_stride: int,
                         pitch: int, shard_len: int, stripes: int, erased: Optional[bytes] = None,
                         stream: int = 0):
@@ -843,7 +929,7 @@ class FEC:
      STAT_SCRUB_REGENERATED, STAT_COMBINE_JOBS, STAT_COMBINE_ROWS, STAT_UPDATE_DEGRADED,
      STAT_UPDATE_ABSORBED, STAT_COLUMN_STRIPES, STAT_COLUMN_BYTES, STAT_BATCH_LENS_PASSES,
      STAT_COMBINE_LENS_LAUNCHES, STAT_REPAIR_CHECKED, STAT_SCRUB_LENS_LAUNCHES,
-     STAT_COLUMN_LENS_LAUNCHES) = range(29)
+     STAT_COLUMN_LENS_LAUNCHES, STAT_CRC_SECTORS, STAT_CRC_REGENERATED) = range(31)
 
     def stat(self, which: int) -> int:
         return _lib().rs_stat(self._h, which)
@@ -975,6 +1061,17 @@ def blake2b_host(messages: Sequence[bytes], digest_len: int = 32, threads: int =
     _check(_lib().rs_blake2b_host(len(messages), ptrs, lens, digest_len, ctypes.cast(out, ctypes.c_void_p),
                                   threads), "rs_blake2b_host")
     return _split(out.raw, len(messages), digest_len)
+
+
+def crc32c_host(buffers: Sequence[bytes]) -> List[int]:
+    """rs_crc32c_host: CRC-32C (RFC 3720) of each buffer on the host CPU (no
+    context, no GPU): the reference of the sector checksums."""
+    if not buffers:
+        return []
+    keep, ptrs, lens = _message_table(buffers)
+    out = (ctypes.c_uint32 * len(buffers))()
+    _check(_lib().rs_crc32c_host(len(buffers), ptrs, lens, ctypes.cast(out, ctypes.c_void_p)), "rs_crc32c_host")
+    return list(out)
 
 
 def NewFEC(k: int, n: int) -> FEC:
