@@ -96,7 +96,12 @@ const char *rs_strerror(int status);
  * which = 11 that serves rs_correct_columns_ptrs_lens calls of mixed lengths,
  * e.g. "columns_MG4_B256_ptrs_lens" ("none" for m > 16); which = 18 and 19:
  * the sector-checksum kernel of the rs_crc32c_* calls and its pointer-mode
- * twin, "crc32c_H16_B256" and "crc32c_H16_B256_ptrs". */
+ * twin, "crc32c_H16_B256" and "crc32c_H16_B256_ptrs"; which = 20, 21 and 22:
+ * the kernels that serve rs_encode_ptrs, rs_update_ptrs and rs_read_ptrs --
+ * 20 is the name of which = 0 for a split-table code (that kernel reads the
+ * table itself) and the generated pointer-mode twin for a bit-sliced one, e.g.
+ * "bitslice_k64_m16_ptrs"; 21 and 22 are the pointer-mode twins of which = 3
+ * and 4, e.g. "update_MG4_B256_ptrs" and "read_K10_MG4_B256_ptrs". */
 const char *rs_kernel_name(const rs_ctx *ctx, int which);
 
 /* ---- host-buffer API (the cgo path) -------------------------------------
@@ -677,6 +682,77 @@ int rs_reconstruct_checked_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t 
                                 const uint8_t *erased, uint32_t *first_bad, void *stream);
 int rs_correct_columns_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes,
                             const uint8_t *erased, int *status, uint32_t *corrected, void *stream);
+
+/* The first half of a store's life on the pointer placement: write parity for
+ * new stripes, overwrite shards in place, serve reads while shards are
+ * missing.  shard_ptrs as for rs_verify_ptrs (DEVICE, [stripes][n], 8-byte
+ * aligned, 16-byte-aligned addresses), and "the slot of shard i of stripe s"
+ * is shard_ptrs[s * n + i].  The table is only read, and only by kernels: the
+ * host never copies it back, so a caller needs no host copy of it, and all
+ * three calls are enqueued on stream and return when queued (the small job
+ * tables are staged through pinned memory).  Safe from several threads on one
+ * ctx; a device set routes by the table's device.
+ * Refused by all three with nothing launched or written: RS_EINVAL for a NULL
+ * ctx, a NULL or misaligned table, 2^28 or more 16-byte columns, stripes >=
+ * 2^32, or more than 2^31 - 1 blocks.  RS_OK with nothing launched for
+ * stripes == 0 or shard_len == 0, and count == 0 where there is a list.
+ * The caller guarantees what the host cannot check, because the table lives
+ * on the device: the ranges of the slots a call touches do not overlap each
+ * other (as for rs_correct_columns_ptrs), and no src or dst range meets one.
+ *
+ * rs_encode_ptrs is rs_encode_stripes on that placement: parity shard r of
+ * stripe s is written at shard_ptrs[s * n + k + r], and its round_up(shard_len,
+ * 16) bytes are bit for bit what rs_encode_stripes writes for the same data.
+ * The k data shards of every stripe are only read and nothing else is written;
+ * a stripe moves (k + m) * S bytes.  The kernel is the one that serves
+ * rs_encode_stripes for the code: the split-table kernel reading the table, or
+ * the generated twin of the bit-sliced network (rs_kernel_name which = 20).
+ * m == 0: RS_OK.  No lock and no lease, as rs_encode_stripes.
+ *
+ * rs_update_ptrs is rs_update_stripes on that placement, for stripes without
+ * missing shards: `updates` and its validation are those of rs_update_stripes
+ * (RS_EINVAL for NULL updates, stripe >= stripes, a duplicate (stripe, shard),
+ * a NULL or misaligned src, reserved != 0; RS_EBAD_SHARE_ID for shard >= k),
+ * except that a src range cannot be checked against the slots.  For each entry
+ * the slot of data shard `shard` of stripe `stripe` takes the contents at src,
+ * and every parity shard r of that stripe becomes
+ *     parity[r] ^= E[k + r][shard] * (old ^ new);
+ * a stripe with j changed shards moves (3j + 2m) * S bytes.  Only the table
+ * entries of a listed stripe's changed shards and of its m parity shards are
+ * loaded: every other entry -- the stripe's other data shards, every entry of
+ * an unlisted stripe -- is never dereferenced and may hold anything.  With
+ * m == 0 only the data is overwritten.
+ * Slices: the call works on bytes [shard_offset, shard_offset + shard_len) of
+ * every slot it touches, and src holds the slice's new bytes from its start
+ * (rs_update_stripes advances data and parity instead; a table cannot be
+ * advanced without a second table).  shard_offset is a multiple of 16 and
+ * shard_offset / 16 plus the column count stays below 2^28, else RS_EINVAL.
+ * There is no pointer form of rs_update_degraded.  A stripe with an erased
+ * changed shard takes two passes: rs_read_ptrs regenerates the old contents
+ * into scratch (no host copy of the table needed for that half), then
+ * rs_combine applies the deltas to the present parity, whose addresses the
+ * caller names (DESIGN.md 4.15 measured that route at 0.78 / 0.77 of the HBM
+ * peak where the fused strided kernel runs at 0.58 / 0.25).
+ *
+ * rs_read_ptrs is rs_read_stripes on that placement: erased (HOST, stripes * n
+ * flags, not NULL), `reads` and its validation are those of rs_read_stripes
+ * (RS_EINVAL for NULL erased or reads, stripe >= stripes, a duplicate (stripe,
+ * shard), a NULL or misaligned dst, reserved != 0, two dst ranges that meet;
+ * RS_EBAD_SHARE_ID for shard >= n; RS_ENOT_ENOUGH for a listed stripe that
+ * wants an erased shard and has more than m erasures; a listed stripe with
+ * more than m erasures that wants present shards only is served), except that
+ * a dst range cannot be checked against the slots.  A present wanted shard is
+ * copied; an erased one is computed from the k survivors Rebuild chooses, with
+ * the row of the shared pattern cache; a stripe with j wanted missing shards
+ * moves (k + j) * S bytes.  Nothing named by the table is written, and the
+ * table entries of erased shards are never loaded.  shard_offset as for
+ * rs_update_ptrs: bytes [shard_offset, shard_offset + shard_len) of the slots
+ * are read and dst receives the slice from its start. */
+int rs_encode_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_len, size_t stripes, void *stream);
+int rs_update_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_offset, size_t shard_len, size_t stripes,
+                   const rs_shard_update *updates, size_t count, void *stream);
+int rs_read_ptrs(rs_ctx *ctx, const uint64_t *shard_ptrs, size_t shard_offset, size_t shard_len, size_t stripes,
+                 const uint8_t *erased, const rs_shard_read *reads, size_t count, void *stream);
 
 /* rs_verify_ptrs and rs_reconstruct_checked_ptrs for stripes that each have a
  * shard length of their own (a store of objects of different sizes, scrubbed

@@ -40,6 +40,20 @@ struct BitsliceArgs {
 
 using BitsliceLaunch = hipError_t (*)(const BitsliceArgs&, hipStream_t);
 
+// The encode of the pointer placement (rs_encode_ptrs): shard i of stripe s is
+// at shard_ptrs[s * (k + m) + i] (device table, only read; 16-byte-aligned
+// addresses).  Served by the encode kernel's generated twin, whose network is
+// the same text.
+struct BitslicePtrArgs {
+    const uint64_t* shard_ptrs;
+    uint64_t stripes;
+    uint32_t ncols16;      // 16-byte columns per shard (ceil(S / 16))
+    uint32_t blocks_per_stripe;
+    uint32_t xcd;          // as BitsliceArgs
+};
+
+using BitslicePtrLaunch = hipError_t (*)(const BitslicePtrArgs&, hipStream_t);
+
 // Per-descriptor record of what Rebuild does with the stripe's pattern
 // (k <= 64, m <= 32), written by the host next to the stripe descriptor so a
 // block knows which inputs to load from the same scalar load round trip as
@@ -94,6 +108,8 @@ struct BitsliceKernel {
     int rec_tops[4];
     BitsliceRecLaunch rec_top_launch[4];
     const char* rec_top_names[4];
+    const char* ptrs_name;          // "bitslice_k<k>_m<m>_ptrs": the encode's pointer-placement twin
+    BitslicePtrLaunch ptrs_launch;
 };
 
 // Generated kernel for encode of (k, k+m), or nullptr.

@@ -269,6 +269,19 @@ __device__ __forceinline__ void bs_store(uint8_t* shard, uint32_t off, uint32_t 
         std::fprintf(f, "    ca = blk * 512u + wave * 64u + lane;\n    cb = ca + 256u;\n}\n\n");
     else
         std::fprintf(f, "    ca = blk * 512u + wave * 128u + lane;\n    cb = ca + 64u;\n}\n\n");
+    std::fputs("// Pointer placement (the _ptrs encode twins): entry i of a stripe's row of the\n"
+               "// shard table, the same for every lane of the block.  The table is only read\n"
+               "// while a kernel runs, so it is loaded through the constant address space:\n"
+               "// scalar loads, which wait on lgkmcnt and leave the shard loads in flight\n"
+               "// (behind a BS_FENCE a plain load becomes a vector load and a vmcnt(0)).\n"
+               "typedef __attribute__((address_space(4))) const uint64_t BsConstU64;\n"
+               "__device__ __forceinline__ uint8_t* bs_tab(const uint64_t* row, uint32_t i) {\n"
+               "    const uint64_t v = *(BsConstU64*)(row + i);\n"
+               "    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));\n"
+               "    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));\n"
+               "    return reinterpret_cast<uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);\n"
+               "}\n\n",
+               f);
 }
 
 // Pins accumulators [o0, o1) (multiples of 8): a shard's XORs complete
@@ -325,18 +338,31 @@ void emit_network(FILE* f, const std::vector<uint8_t>& E, int k, int m, int j, b
     }
 }
 
-void emit_kernel(FILE* f, int k, int n) {
+// ptrs: the encode's twin for the pointer placement (rs_encode_ptrs,
+// BitslicePtrArgs).  Shard i of stripe s is at a.shard_ptrs[s * n + i]: the
+// strided kernel's d + j * pitch and p + t * pitch become entries of the
+// stripe's table row, each resolved where the strided kernel forms the
+// address.  Everything else, the network included, is the same text.
+void emit_kernel(FILE* f, int k, int n, bool ptrs = false) {
     const int m = n - k;
     const std::vector<uint8_t> E = rsmi::systematic_matrix(k, n);
-    const std::string name = "rs_bitslice_k" + std::to_string(k) + "_m" + std::to_string(m);
+    const std::string name =
+        "rs_bitslice_k" + std::to_string(k) + "_m" + std::to_string(m) + (ptrs ? "_ptrs" : "");
     const int P = m * 8;  // output planes
+    // The address of data shard j.
+    auto shard = [&](int j) {
+        return ptrs ? "bs_tab(tp, " + std::to_string(j) + "u)" : "d + " + std::to_string(j) + "u * a.pitch";
+    };
 
-    std::fprintf(f, "const uint8_t %s_matrix[%d] = {", name.c_str(), m * k);
-    for (int i = 0; i < m * k; ++i)
-        std::fprintf(f, "%s%u", i ? "," : "", E[static_cast<size_t>(k) * k + i]);
-    std::fprintf(f, "};\n\n");
+    if (!ptrs) {
+        std::fprintf(f, "const uint8_t %s_matrix[%d] = {", name.c_str(), m * k);
+        for (int i = 0; i < m * k; ++i)
+            std::fprintf(f, "%s%u", i ? "," : "", E[static_cast<size_t>(k) * k + i]);
+        std::fprintf(f, "};\n\n");
+    }
 
-    std::fprintf(f, "__global__ __launch_bounds__(256) void %s(BitsliceArgs a) {\n", name.c_str());
+    std::fprintf(f, "__global__ __launch_bounds__(256) void %s(%s a) {\n", name.c_str(),
+                 ptrs ? "BitslicePtrArgs" : "BitsliceArgs");
     std::fprintf(f,
                  "    // A stripe's blocks run on one XCD, in order (xcd.hpp).\n"
                  "    const uint32_t bx = a.xcd ? xcd_block(blockIdx.x, a.xcd * a.blocks_per_stripe, gridDim.x) : blockIdx.x;\n"
@@ -347,20 +373,24 @@ void emit_kernel(FILE* f, int k, int n) {
                  "    uint32_t ca, cb;\n"
                  "    bs_cols(blk, wave, lane, ca, cb);\n"
                  "    if (ca > last) return;  // whole 16-B columns past the shard: nothing to code\n"
-                 "    const uint32_t offa = ca * 16u, offb = (cb <= last ? cb : last) * 16u;\n"
-                 "    const uint8_t* d = a.data + s * a.data_ss;\n"
-                 "    uint8_t* p = a.parity + s * a.parity_ss;\n"
+                 "    const uint32_t offa = ca * 16u, offb = (cb <= last ? cb : last) * 16u;\n");
+    if (ptrs)
+        std::fprintf(f, "    const uint64_t* tp = a.shard_ptrs + s * %du;\n", n);
+    else
+        std::fprintf(f, "    const uint8_t* d = a.data + s * a.data_ss;\n"
+                        "    uint8_t* p = a.parity + s * a.parity_ss;\n");
+    std::fprintf(f,
                  "    uint32_t acc[%d];\n"
                  "    uint32_t x[%d][8];\n",
                  P, kPrefetch + 1);
     for (int j = 0; j < kPrefetch && j < k; ++j)
-        std::fprintf(f, "    bs_load(x[%d], d + %du * a.pitch, offa, offb);\n", j, j);
+        std::fprintf(f, "    bs_load(x[%d], %s, offa, offb);\n", j, shard(j).c_str());
     for (int j = 0; j < k; ++j) {
         const int buf = j % (kPrefetch + 1);
         std::fprintf(f, "    // shard %d\n    BS_FENCE();\n", j);
         if (j + kPrefetch < k)
-            std::fprintf(f, "    bs_load(x[%d], d + %du * a.pitch, offa, offb);\n", (j + kPrefetch) % (kPrefetch + 1),
-                         j + kPrefetch);
+            std::fprintf(f, "    bs_load(x[%d], %s, offa, offb);\n", (j + kPrefetch) % (kPrefetch + 1),
+                         shard(j + kPrefetch).c_str());
         // The shard's words enter the XOR network only here, so its transpose
         // is not hoisted next to the loads (which would wait for the prefetch).
         std::fprintf(f, "    asm volatile(\"\" : \"+v\"(x[%d][0]), \"+v\"(x[%d][1]), \"+v\"(x[%d][2]), \"+v\"(x[%d][3]), "
@@ -387,20 +417,24 @@ void emit_kernel(FILE* f, int k, int n) {
     std::fprintf(f,
                  "        uint32_t w[8] = {acc[8 * r], acc[8 * r + 1], acc[8 * r + 2], acc[8 * r + 3],\n"
                  "                         acc[8 * r + 4], acc[8 * r + 5], acc[8 * r + 6], acc[8 * r + 7]};\n"
-                 "        bs_from_planes(w);\n"
-                 "        uint8_t* o = p + static_cast<uint64_t>(t) * a.pitch;\n"
+                 "        bs_from_planes(w);\n");
+    if (ptrs)
+        std::fprintf(f, "        uint8_t* o = bs_tab(tp, %du + static_cast<uint32_t>(t));\n", k);
+    else
+        std::fprintf(f, "        uint8_t* o = p + static_cast<uint64_t>(t) * a.pitch;\n");
+    std::fprintf(f,
                  "        bs_store(o, offa, w[0], w[1], w[2], w[3]);\n"
                  "        if (okb) bs_store(o, offb, w[4], w[5], w[6], w[7]);\n"
                  "    }\n}\n\n");
 
     std::fprintf(f,
-                 "hipError_t launch_%s(const BitsliceArgs& a, hipStream_t stream) {\n"
+                 "hipError_t launch_%s(const %s& a, hipStream_t stream) {\n"
                  "    const uint64_t blocks = a.stripes * a.blocks_per_stripe;\n"
                  "    if (blocks == 0) return hipSuccess;\n"
                  "    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;\n"
                  "    hipLaunchKernelGGL(%s, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, a);\n"
                  "    return hipGetLastError();\n}\n\n",
-                 name.c_str(), name.c_str());
+                 name.c_str(), ptrs ? "BitslicePtrArgs" : "BitsliceArgs", name.c_str());
 }
 
 // Bit-sliced reconstruct (bitslice.hpp): inputs are the present data shards
@@ -1055,6 +1089,7 @@ int main(int argc, char** argv) {
     };
     for (auto [k, n] : codes) {
         emit_kernel(f, k, n);
+        emit_kernel(f, k, n, true);
         if (k <= kRecMaxK && n - k <= kRecMaxM) {
             emit_reconstruct(f, k, n, n - k);
             for (int top : tops_of(n - k)) emit_reconstruct(f, k, n, top);
@@ -1078,13 +1113,15 @@ int main(int argc, char** argv) {
             tv += "}";
             tl += "}";
             tn += "}";
-            std::fprintf(f, "        {%d, %d, \"%s\", %s_matrix, launch_%s, \"%s\", launch_%s, %d, %zu, %s, %s, %s},\n", k, m,
+            std::fprintf(f, "        {%d, %d, \"%s\", %s_matrix, launch_%s, \"%s\", launch_%s, %d, %zu, %s, %s, %s,\n"
+                            "         \"%s_ptrs\", launch_%s_ptrs},\n", k, m,
                          name.c_str() + 3, name.c_str(), name.c_str(), rec.c_str() + 3, rec.c_str(), kRecIters, tops.size(),
                          tops.empty() ? "{}" : tv.c_str(), tops.empty() ? "{}" : tl.c_str(),
-                         tops.empty() ? "{}" : tn.c_str());
+                         tops.empty() ? "{}" : tn.c_str(), name.c_str() + 3, name.c_str());
         } else {
-            std::fprintf(f, "        {%d, %d, \"%s\", %s_matrix, launch_%s, nullptr, nullptr, 1, 0, {}, {}, {}},\n", k, m,
-                         name.c_str() + 3, name.c_str(), name.c_str());
+            std::fprintf(f, "        {%d, %d, \"%s\", %s_matrix, launch_%s, nullptr, nullptr, 1, 0, {}, {}, {},\n"
+                            "         \"%s_ptrs\", launch_%s_ptrs},\n", k, m,
+                         name.c_str() + 3, name.c_str(), name.c_str(), name.c_str() + 3, name.c_str());
         }
     }
     std::fprintf(f, "    };\n    for (const BitsliceKernel& b : table)\n"

@@ -487,8 +487,20 @@ __global__ __launch_bounds__(64) void gather_columns_masked_kernel(const uint8_t
 // the inputs are old ^ new, the coefficients single columns of the encode
 // matrix, and the accumulators go back to the addresses they came from.
 // LDS: [j][MG/4][20] table dwords | j old-shard pointers | j new-shard pointers.
-template <int MG, int BT, bool NT>
-__global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
+//
+// PTRS (compile-time twin, launch_update_ptrs): shard id of stripe s is at
+// a.shard_ptrs[s * n + id] and the layout fields of `a` are unused.  The block
+// loads the table entries of its job's changed shards -- their ids first, then
+// their addresses, as the check kernel's oid[] / dp[] -- and of its group's eg
+// parity rows, and no other entry of the table.  a.shard_off, the byte offset
+// of the call's slice within every slot, is added once to each resolved base;
+// a src holds the slice from its start.
+struct UpdPtrArgs : UpdArgs {
+    const uint64_t* shard_ptrs;
+    uint64_t shard_off;
+};
+template <int MG, int BT, bool NT, bool PTRS = false>
+__global__ __launch_bounds__(BT) void rs_update_kernel(std::conditional_t<PTRS, UpdPtrArgs, UpdArgs> a) {
     extern __shared__ uint4 lds4[];
     static_assert(MG % 4 == 0, "whole sub-steps");
     constexpr int TG = MG / kRowsPerStep;  // sub-steps per changed shard
@@ -515,17 +527,45 @@ __global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
     uint32_t* tw = reinterpret_cast<uint32_t*>(lds4);
     uint8_t** optr = reinterpret_cast<uint8_t**>(tw + j * TG * kStepWords);
     uint8_t** nptr = optr + j;
-    uint8_t* dbase = a.data + s * a.data_ss;
-    for (int i = threadIdx.x; i < j; i += BT) {
-        const UpdateEntry e = ent[i];
-        optr[i] = dbase + static_cast<uint64_t>(e.shard) * a.pitch;
-        nptr[i] = reinterpret_cast<uint8_t*>(e.src);
-    }
+    uint8_t* dbase = nullptr;      // strided layout: the stripe's data
+    const uint64_t* tp = nullptr;  // pointer mode: the stripe's row of the shard table
     // Parity rows of this group; rows past eg are never dereferenced.
     uint8_t* pp[MG];
+    // The first JB changed shards, resolved ahead of the LDS pointer arrays
+    // for the loads that go out before the table build.
+    uint8_t* po[JB];
+    uint8_t* pn[JB];
+    if constexpr (PTRS) {
+        tp = a.shard_ptrs + s * (a.k + a.m);
+        // Ids first, then every address the first iteration needs in one batch
+        // of scalar loads: the group's parity rows and the first JB old
+        // shards.  A row past eg or a shard past j takes the index of the last
+        // real one -- an entry the block loads anyway, so that the batch has
+        // no branches and never leaves the job's entries of the table -- and
+        // is never dereferenced.
+        uint32_t sh[JB];
 #pragma unroll
-    for (int r = 0; r < MG; ++r)
-        pp[r] = uniform_ptr(a.parity + s * a.parity_ss + static_cast<uint64_t>(row0 + r) * a.pitch);
+        for (int q = 0; q < JB; ++q) {
+            const UpdateEntry e = ent[min(q, j - 1)];
+            sh[q] = __builtin_amdgcn_readfirstlane(e.shard);
+            pn[q] = uniform_ptr(reinterpret_cast<uint8_t*>(e.src));
+        }
+#pragma unroll
+        for (int r = 0; r < MG; ++r)
+            pp[r] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[a.k + row0 + min(r, eg - 1)])) + a.shard_off;
+#pragma unroll
+        for (int q = 0; q < JB; ++q) po[q] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[sh[q]])) + a.shard_off;
+    } else {
+        dbase = a.data + s * a.data_ss;
+        for (int i = threadIdx.x; i < j; i += BT) {
+            const UpdateEntry e = ent[i];
+            optr[i] = dbase + static_cast<uint64_t>(e.shard) * a.pitch;
+            nptr[i] = reinterpret_cast<uint8_t*>(e.src);
+        }
+#pragma unroll
+        for (int r = 0; r < MG; ++r)
+            pp[r] = uniform_ptr(a.parity + s * a.parity_ss + static_cast<uint64_t>(row0 + r) * a.pitch);
+    }
 
     const uint32_t last = a.ncols16 - 1;
     const uint32_t cstride = a.chunks * BT;
@@ -554,10 +594,25 @@ __global__ __launch_bounds__(BT) void rs_update_kernel(UpdArgs a) {
 #pragma unroll
     for (int q = 0; q < JB; ++q) {
         if (q >= j) break;
-        const UpdateEntry e = ent[q];
-        const uint32_t sh = __builtin_amdgcn_readfirstlane(e.shard);
-        xo[q] = gload16<NT>(uniform_ptr(dbase + static_cast<uint64_t>(sh) * a.pitch) + off0);
-        xn[q] = gload16<NT>(uniform_ptr(reinterpret_cast<uint8_t*>(e.src)) + off0);
+        if constexpr (PTRS) {
+            xo[q] = gload16<NT>(po[q] + off0);
+            xn[q] = gload16<NT>(pn[q] + off0);
+        } else {
+            const UpdateEntry e = ent[q];
+            const uint32_t sh = __builtin_amdgcn_readfirstlane(e.shard);
+            xo[q] = gload16<NT>(uniform_ptr(dbase + static_cast<uint64_t>(sh) * a.pitch) + off0);
+            xn[q] = gload16<NT>(uniform_ptr(reinterpret_cast<uint8_t*>(e.src)) + off0);
+        }
+    }
+    if constexpr (PTRS) {
+        // The LDS pointer arrays (later iterations, shards past JB, the commit)
+        // take two dependent vector loads per entry: behind the loads above,
+        // not in front of them.
+        for (int i = threadIdx.x; i < j; i += BT) {
+            const UpdateEntry e = ent[i];
+            optr[i] = reinterpret_cast<uint8_t*>(tp[e.shard]) + a.shard_off;
+            nptr[i] = reinterpret_cast<uint8_t*>(e.src);
+        }
     }
     // Split tables: sub-step (c, g) holds E[k + row0 + 4g .. + 3][shard_c].
     for (int idx = threadIdx.x; idx < j * MG; idx += BT) {
@@ -1015,8 +1070,24 @@ __global__ __launch_bounds__(BT) void rs_update_degraded_kernel(DegArgs a) {
 // One sub-step per survivor (MG = 4) and only the group's eg wanted rows are
 // multiplied (mac_step_rows) whatever K is: the common read wants one row.
 // LDS: [k][20] table dwords | k survivor pointers.
-template <int K, int MG, int BT, bool NT>
-__global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
+//
+// PTRS (compile-time twin, launch_read_ptrs): shard id of stripe s is at
+// a.shard_ptrs[s * n + id] and the layout fields of `a` are unused.  The
+// survivors' addresses are resolved exactly as rs_check_kernel<..., PTRS>
+// resolves them: one batch of scalar loads from the table behind the batch of
+// ids (K <= 16), or the LDS pointer array -- and there the first 4 survivors by
+// scalar loads too, their first loads ahead of the barrier (kEarly below), which
+// the check kernel's twin does not do.  a.shard_off, the byte offset of the
+// call's slice within every slot, is added once to each resolved base.
+// entries[..].dst stays a real destination and receives the slice from its
+// start.  The table entries of erased shards are never loaded: the pattern's
+// survivors are all present.
+struct ReadPtrArgs : ReadArgs {
+    const uint64_t* shard_ptrs;
+    uint64_t shard_off;
+};
+template <int K, int MG, int BT, bool NT, bool PTRS = false>
+__global__ __launch_bounds__(BT) void rs_read_kernel(std::conditional_t<PTRS, ReadPtrArgs, ReadArgs> a) {
     extern __shared__ uint4 lds4[];
     static_assert(MG == kRowsPerStep, "one table sub-step per survivor");
     constexpr bool kRegPtrs = K > 0 && K <= 16;           // survivor bases kept in SGPRs
@@ -1053,22 +1124,43 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
     }
 
     const uint32_t* srcid = a.src + static_cast<size_t>(pat) * k;
-    uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
-    uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
     uint8_t* sp[kRegPtrs ? K : 1];
-    if constexpr (kRegPtrs) {
-        uint32_t ids[K];
+    // The twin's LDS pointer path: its fill takes two dependent vector loads
+    // per survivor (id, then table entry) where the strided kernel's takes
+    // one, so the first EB survivors are resolved by scalar loads as well and
+    // their first-iteration loads go out ahead of the fill, the table build
+    // and the barrier (below, where off0 is known).
+    constexpr bool kEarly = PTRS && !kRegPtrs;
+    // Early survivors: 4 of the batch's JB = 8.  All 8 cost 135 VGPRs against
+    // the strided kernel's 103 -- past 128, a wave per SIMD less.
+    constexpr int EB = 4;
+    const uint64_t* tp = nullptr;  // pointer mode: the stripe's row of the shard table
+    if constexpr (PTRS) {
+        tp = a.shard_ptrs + s * (a.k + a.m);
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
 #pragma unroll
-        for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
 #pragma unroll
-        for (int c = 0; c < K; ++c)
-            sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
-                                                     : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+            for (int c = 0; c < K; ++c) sp[c] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[ids[c]])) + a.shard_off;
+        }
     } else {
-        for (int i = threadIdx.x; i < k; i += BT) {
-            const uint32_t id = srcid[i];
-            sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
-                               : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+        uint8_t* dbase = const_cast<uint8_t*>(a.data) + s * a.data_ss;
+        uint8_t* pbase = const_cast<uint8_t*>(a.parity) + s * a.parity_ss;
+        if constexpr (kRegPtrs) {
+            uint32_t ids[K];
+#pragma unroll
+            for (int c = 0; c < K; ++c) ids[c] = __builtin_amdgcn_readfirstlane(srcid[c]);
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+                sp[c] = ids[c] < static_cast<uint32_t>(K) ? dbase + static_cast<uint64_t>(ids[c]) * a.pitch
+                                                         : pbase + static_cast<uint64_t>(ids[c] - K) * a.pitch;
+        } else {
+            for (int i = threadIdx.x; i < k; i += BT) {
+                const uint32_t id = srcid[i];
+                sptr[i] = id < a.k ? dbase + static_cast<uint64_t>(id) * a.pitch
+                                   : pbase + static_cast<uint64_t>(id - a.k) * a.pitch;
+            }
         }
     }
     const uint32_t last = a.ncols16 - 1;
@@ -1081,6 +1173,22 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
     if constexpr (kRegPtrs) {
 #pragma unroll
         for (int c = 0; c < K; ++c) xpre[c] = gload16<NT>(sp[c] + off0);
+    }
+    uint4 xe[kEarly ? EB : 1];
+    if constexpr (kEarly) {
+        // A survivor past k (runtime k < EB) takes the index of the last one:
+        // a batch without branches that stays within the entries the block
+        // loads anyway; its column is loaded and never used.
+        uint32_t ids[EB];
+#pragma unroll
+        for (int q = 0; q < EB; ++q) ids[q] = __builtin_amdgcn_readfirstlane(srcid[min(q, k - 1)]);
+        uint8_t* pe[EB];
+#pragma unroll
+        for (int q = 0; q < EB; ++q) pe[q] = uniform_ptr(reinterpret_cast<uint8_t*>(tp[ids[q]])) + a.shard_off;
+#pragma unroll
+        for (int q = 0; q < EB; ++q) xe[q] = gload16<NT>(pe[q] + off0);
+        for (int i = threadIdx.x; i < k; i += BT)
+            sptr[i] = reinterpret_cast<uint8_t*>(tp[srcid[i]]) + a.shard_off;
     }
     // Destinations of the group's wanted rows; rows past eg have none.
     uint8_t* dp[MG];
@@ -1118,7 +1226,17 @@ __global__ __launch_bounds__(BT) void rs_read_kernel(ReadArgs a) {
         for (int jb = 0; jb < k; jb += JB) {
             uint4 xb[kRegPtrs ? 1 : JB];
             uint4* x = kRegPtrs ? xpre : xb;
-            if constexpr (!kRegPtrs) {
+            if constexpr (kEarly) {
+                // The first EB columns of the block's first batch were loaded
+                // ahead of the table build (off == off0 there).
+                const bool early = it == 0 && jb == 0;
+#pragma unroll
+                for (int q = 0; q < JB; ++q) {
+                    if (K == 0 && jb + q >= k) break;
+                    if (q < EB && early) x[q] = xe[q];
+                    else x[q] = gload16<NT>(uniform_ptr(sptr[jb + q]) + off);
+                }
+            } else if constexpr (!kRegPtrs) {
 #pragma unroll
                 for (int q = 0; q < JB; ++q) {
                     if (K == 0 && jb + q >= k) break;
@@ -1830,8 +1948,12 @@ struct UpdateVariant {
     int MG;
     const char* name;
     void (*fn)(UpdArgs);
+    const char* ptrs_name;  // the pointer-mode twin
+    void (*ptrs_fn)(UpdPtrArgs);
 };
-#define RS_UPDATE(MG) {MG, "update_MG" #MG "_B256", rs_update_kernel<MG, kBlock, true>}
+#define RS_UPDATE(MG)                                                                       \
+    {MG, "update_MG" #MG "_B256", rs_update_kernel<MG, kBlock, true>, "update_MG" #MG "_B256_ptrs", \
+     rs_update_kernel<MG, kBlock, true, true>}
 const UpdateVariant kUpdate[] = {RS_UPDATE(4), RS_UPDATE(8), RS_UPDATE(16)};
 #undef RS_UPDATE
 
@@ -1904,8 +2026,12 @@ struct ReadVariant {
     int K;
     const char* name;
     void (*fn)(ReadArgs);
+    const char* ptrs_name;  // the pointer-mode twin
+    void (*ptrs_fn)(ReadPtrArgs);
 };
-#define RS_READ(K) {K, "read_K" #K "_MG4_B256", rs_read_kernel<K, 4, kBlock, true>}
+#define RS_READ(K)                                                                                 \
+    {K, "read_K" #K "_MG4_B256", rs_read_kernel<K, 4, kBlock, true>, "read_K" #K "_MG4_B256_ptrs", \
+     rs_read_kernel<K, 4, kBlock, true, true>}
 const ReadVariant kRead[] = {RS_READ(10), RS_READ(4), RS_READ(8), RS_READ(64), RS_READ(0)};
 #undef RS_READ
 constexpr int kReadMG = 4;
@@ -1966,7 +2092,11 @@ const RepairVariant& pick_repair(int k) {
 
 const char* update_variant_name(int m) { return pick_update(m, 0).name; }
 
+const char* update_ptrs_variant_name(int m) { return pick_update(m, 0).ptrs_name; }
+
 const char* read_variant_name(int k) { return pick_read(k).name; }
+
+const char* read_ptrs_variant_name(int k) { return pick_read(k).ptrs_name; }
 
 const char* check_variant_name(int k) { return pick_check(k).name; }
 
@@ -2100,6 +2230,21 @@ hipError_t launch_read(const ReadArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_read_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint64_t shard_off, hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.groups == 0) return hipSuccess;
+    if (!shard_ptrs || (shard_off & 15u)) return hipErrorInvalidValue;
+    const ReadVariant& v = pick_read(static_cast<int>(a.k));
+    const size_t lds = static_cast<size_t>(a.k) * kStepWords * 4 + a.k * sizeof(void*);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    ReadPtrArgs pa{};
+    static_cast<ReadArgs&>(pa) = a;
+    pa.shard_ptrs = shard_ptrs;
+    pa.shard_off = shard_off;
+    hipLaunchKernelGGL(v.ptrs_fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, pa);
+    return hipGetLastError();
+}
+
 bool plan_update(UpdArgs* a, uint32_t max_j) {
     const UpdateVariant& v = pick_update(static_cast<int>(a->m), max_j);
     const uint32_t total_it = (a->ncols16 + kBlock - 1) / kBlock;
@@ -2128,6 +2273,24 @@ hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream) {
     const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
     if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(v->fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_ptrs(const UpdArgs& a, const uint64_t* shard_ptrs, uint64_t shard_off, uint32_t max_j,
+                              hipStream_t stream) {
+    if (a.njobs == 0 || a.ncols16 == 0 || a.m == 0 || max_j == 0) return hipSuccess;
+    if (!shard_ptrs || (shard_off & 15u)) return hipErrorInvalidValue;
+    const UpdateVariant* v = nullptr;
+    for (const UpdateVariant& u : kUpdate)
+        if (static_cast<uint32_t>(u.MG) == a.mg) v = &u;
+    const size_t lds = update_lds(static_cast<int>(a.mg), max_j);
+    const uint64_t blocks = static_cast<uint64_t>(a.njobs) * a.chunks * a.groups;
+    if (!v || lds > kUpdateLdsMax || blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    UpdPtrArgs pa{};
+    static_cast<UpdArgs&>(pa) = a;
+    pa.shard_ptrs = shard_ptrs;
+    pa.shard_off = shard_off;
+    hipLaunchKernelGGL(v->ptrs_fn, dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), lds, stream, pa);
     return hipGetLastError();
 }
 
@@ -2274,18 +2437,27 @@ hipError_t launch_mailbox(MailboxHost* h, MailboxDev* d, const MailboxJobs& jobs
     return hipGetLastError();
 }
 
-hipError_t launch_matmul(MatArgs a, int max_e, hipStream_t stream) {
-    if (a.stripes == 0 || a.ncols16 == 0 || max_e <= 0) return hipSuccess;
-    const Variant& v = pick(static_cast<int>(a.k), max_e);
-    const uint32_t total_it = (a.ncols16 + v.BT - 1) / v.BT;
+namespace {
+// The launch plan of variant v for a (stripes, ncols16 set) coding up to max_e
+// rows per stripe: fills in iters, chunks and groups; the grid's blocks.
+uint64_t plan_matmul(MatArgs* a, const Variant& v, int max_e) {
+    const uint32_t total_it = (a->ncols16 + v.BT - 1) / v.BT;
     static const uint32_t iters_cap = [] {
         const char* e = std::getenv("RSMI_ITERS");  // tuning knob (default 1: one 4 KiB column chunk per block)
         const int v = e ? std::atoi(e) : 1;
         return static_cast<uint32_t>(v > 0 ? v : 1);
     }();
-    a.iters = std::min<uint32_t>(iters_cap, total_it);
-    a.chunks = (total_it + a.iters - 1) / a.iters;
-    a.groups = static_cast<uint32_t>((max_e + v.MG - 1) / v.MG);
+    a->iters = std::min<uint32_t>(iters_cap, total_it);
+    a->chunks = (total_it + a->iters - 1) / a->iters;
+    a->groups = static_cast<uint32_t>((max_e + v.MG - 1) / v.MG);
+    return a->stripes * a->chunks * a->groups;
+}
+}  // namespace
+
+hipError_t launch_matmul(MatArgs a, int max_e, hipStream_t stream) {
+    if (a.stripes == 0 || a.ncols16 == 0 || max_e <= 0) return hipSuccess;
+    const Variant& v = pick(static_cast<int>(a.k), max_e);
+    const uint64_t blocks = plan_matmul(&a, v, max_e);
     size_t lds = static_cast<size_t>(a.k) * ((v.MG + 3) / 4) * kStepWords * 4 + a.k * sizeof(void*);
     static const size_t lds_floor = [] {
         const char* e = std::getenv("RSMI_LDS_PAD_KB");  // A/B knob: LDS per block >= this (caps occupancy)
@@ -2293,11 +2465,18 @@ hipError_t launch_matmul(MatArgs a, int max_e, hipStream_t stream) {
         return static_cast<size_t>(kb > 0 && kb <= 64 ? kb : 0) * 1024;
     }();
     lds = std::max(lds, lds_floor);
-    const uint64_t blocks = a.stripes * a.chunks * a.groups;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     if (a.xcd == ~0u) a.xcd = a.chunks * a.groups;  // a stripe per XCD region
     hipLaunchKernelGGL(v.fn, dim3(static_cast<uint32_t>(blocks)), dim3(v.BT), lds, stream, a);
     return hipGetLastError();
+}
+
+uint64_t matmul_blocks(int k, int max_e, uint32_t ncols16, uint64_t stripes) {
+    if (stripes == 0 || ncols16 == 0 || max_e <= 0) return 0;
+    MatArgs a{};
+    a.stripes = stripes;  // < 2^32, chunks <= 2^20, groups <= 64: no overflow
+    a.ncols16 = ncols16;
+    return plan_matmul(&a, pick(k, max_e), max_e);
 }
 
 hipError_t launch_verify(MatArgs a, uint32_t* first_bad, uint32_t shard_len, hipStream_t stream) {
@@ -2378,7 +2557,41 @@ __global__ __launch_bounds__(256) void copy_pieces_kernel(const uint8_t* src, ui
     const uint4 v = gload16<true>(src + so + static_cast<uint64_t>(col) * 16u);
     gstore16<true>(dst + dof + static_cast<uint64_t>(col) * 16u, v);
 }
+
+// Its twin for the pointer placement: piece i names entry pieces[2i] of the
+// shard table on one side -- the slot, at byte offset slot_off -- and the
+// address pieces[2i+1] on the other.  TO_SLOT: address -> slot (the commit of
+// an update), else slot -> address (the present shards of a read).  Only the
+// table entries the pieces name are loaded.
+template <bool TO_SLOT>
+__global__ __launch_bounds__(256) void copy_table_kernel(const uint64_t* shard_ptrs, const uint64_t* pieces,
+                                                         uint32_t chunks, uint32_t cols16, uint64_t slot_off) {
+    const uint32_t piece = blockIdx.x / chunks;
+    const uint32_t col = (blockIdx.x - piece * chunks) * 256u + threadIdx.x;
+    if (col >= cols16) return;
+    const uint64_t i0 = pieces[2 * piece];
+    const uint64_t idx = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(i0))) |
+                         (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(i0 >> 32)))) << 32);
+    uint8_t* slot = uniform_ptr(reinterpret_cast<uint8_t*>(shard_ptrs[idx])) + slot_off;
+    uint8_t* addr = uniform_ptr(reinterpret_cast<uint8_t*>(pieces[2 * piece + 1]));
+    const uint64_t at = static_cast<uint64_t>(col) * 16u;
+    if constexpr (TO_SLOT) gstore16<true>(slot + at, gload16<true>(addr + at));
+    else gstore16<true>(addr + at, gload16<true>(slot + at));
+}
 }  // namespace
+
+hipError_t launch_copy_table(const uint64_t* shard_ptrs, const uint64_t* pieces, uint32_t count, size_t bytes,
+                             uint64_t slot_off, bool to_slot, hipStream_t stream) {
+    if (count == 0 || bytes == 0) return hipSuccess;
+    if (!shard_ptrs || bytes % 16 != 0 || (slot_off & 15u)) return hipErrorInvalidValue;
+    const uint64_t cols16 = bytes / 16, chunks = (cols16 + 255) / 256;
+    if (cols16 > 0xFFFFFFFFull || static_cast<uint64_t>(count) * chunks > 0x7FFFFFFFull)
+        return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(to_slot ? copy_table_kernel<true> : copy_table_kernel<false>,
+                       dim3(static_cast<uint32_t>(count * chunks)), dim3(256), 0, stream, shard_ptrs, pieces,
+                       static_cast<uint32_t>(chunks), static_cast<uint32_t>(cols16), slot_off);
+    return hipGetLastError();
+}
 
 hipError_t launch_copy_pieces(const uint8_t* src, uint8_t* dst, const uint64_t* pieces, uint32_t count,
                               size_t bytes, hipStream_t stream) {

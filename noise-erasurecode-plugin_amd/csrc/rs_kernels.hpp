@@ -113,6 +113,10 @@ hipError_t launch_mailbox(MailboxHost* h, MailboxDev* d, const MailboxJobs& jobs
 
 // Which compiled variant serves (k, m): "K10_MG4" etc. (diagnostics).
 const char* variant_name(int k, int rows);  // kernel coding up to `rows` outputs per stripe
+// The blocks launch_matmul would launch for `stripes` stripes of ncols16
+// columns and up to max_e outputs (a caller that must refuse a grid of more
+// than 2^31 - 1 blocks before it queues anything; stripes < 2^32).
+uint64_t matmul_blocks(int k, int max_e, uint32_t ncols16, uint64_t stripes);
 
 // Verify twin of the encode launch (a: the encode pattern, all m rows of
 // every stripe, optionally a stripe list {stripe index, 0 << 8 | m}): the
@@ -152,6 +156,17 @@ struct UpdArgs {
 bool plan_update(UpdArgs* a, uint32_t max_j);
 hipError_t launch_update(const UpdArgs& a, uint32_t max_j, hipStream_t stream);  // a: planned
 const char* update_variant_name(int m);  // "update_MG4_B256" etc.
+// Its twin for the pointer placement (rs_update_ptrs): shard i of stripe s is
+// at shard_ptrs[s * (k + m) + i] (device table, only read) and the layout
+// fields of `a` are unused.  The old-shard bases and the row group's parity
+// bases come from the stripe's row of the table, shard_off (a multiple of 16:
+// the byte offset of the call's slice within every slot) added once to each;
+// entries[..].src holds the slice from its start.  Only the entries of a job's
+// changed shards and of its m parity rows are loaded.  A compile-time twin of
+// the update kernel: the strided instantiations keep their code.
+hipError_t launch_update_ptrs(const UpdArgs& a, const uint64_t* shard_ptrs, uint64_t shard_off, uint32_t max_j,
+                              hipStream_t stream);  // a: planned
+const char* update_ptrs_variant_name(int m);  // "update_MG4_B256_ptrs" etc.
 
 // In-place parity update of stripes with missing shards (rs_update_degraded):
 // job b of `jobs` (update_degraded_plan.hpp) patches the present parity rows
@@ -268,6 +283,14 @@ struct ReadArgs {
 bool plan_read(ReadArgs* a, uint32_t max_j);
 hipError_t launch_read(const ReadArgs& a, hipStream_t stream);  // a: planned
 const char* read_variant_name(int k);  // "read_K10_MG4_B256" etc.
+// Its twin for the pointer placement (rs_read_ptrs), as launch_update_ptrs:
+// the survivors' addresses come from the table (resolved as the check
+// kernel's twin resolves them), shard_off added once to each;
+// entries[..].dst stays a destination address and receives the slice from its
+// start.  The table entries of erased shards are never loaded.
+hipError_t launch_read_ptrs(const ReadArgs& a, const uint64_t* shard_ptrs, uint64_t shard_off,
+                            hipStream_t stream);  // a: planned
+const char* read_ptrs_variant_name(int k);  // "read_K10_MG4_B256_ptrs" etc.
 
 // Degraded check (rs_verify_degraded): the verify twin of the read launch,
 // with the same arguments and plan (plan_read).  Job b's entries are the
@@ -356,6 +379,13 @@ hipError_t launch_gather_columns_masked(const MatArgs& a, const uint2* pairs, co
 // with it so PCIe carries only those.
 hipError_t launch_copy_pieces(const uint8_t* src, uint8_t* dst, const uint64_t* pieces, uint32_t count,
                               size_t bytes, hipStream_t stream);
+
+// Its twin for the pointer placement: piece i copies `bytes` bytes between
+// the slot shard_ptrs[pieces[2i]] + slot_off and the address pieces[2i+1] --
+// into the slot (to_slot: the commit of rs_update_ptrs) or out of it (the
+// present shards of rs_read_ptrs).  Only the named table entries are loaded.
+hipError_t launch_copy_table(const uint64_t* shard_ptrs, const uint64_t* pieces, uint32_t count, size_t bytes,
+                             uint64_t slot_off, bool to_slot, hipStream_t stream);
 
 // splitmix64 byte stream fill (bench/test utility).
 hipError_t launch_fill_splitmix(void* dev, size_t len, uint64_t seed, hipStream_t stream);

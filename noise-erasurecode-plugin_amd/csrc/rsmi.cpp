@@ -1206,7 +1206,13 @@ int launch_verify_stripes(const rs_ctx* c, const StripeView& v, size_t stripes, 
 // device in one upload (upload_tables); then the update kernel, then -- when
 // the kernel could not commit the data itself -- the copy of the new shards
 // into place, on the same stream behind it.
-int update_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdatePlan& plan, hipStream_t s) {
+//
+// shard_ptrs: pointer mode (rs_update_ptrs; v is StripeView::ptrs).  The
+// kernel's twin resolves the slots through the table, and the copy commit's
+// pairs are {table index, src} for the table-resolving copy; shard_off is the
+// byte offset of the call's slice within every slot.
+int update_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdatePlan& plan, hipStream_t s,
+                   const uint64_t* shard_ptrs = nullptr, uint64_t shard_off = 0) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size();
     rsmi::UpdArgs a = layout_args<rsmi::UpdArgs>(c, v);
     a.enc = dev_enc(c);
@@ -1226,6 +1232,11 @@ int update_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdateP
         uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
         for (const rsmi::UpdateJob& job : plan.jobs)
             for (uint32_t i = job.first; i < job.first + job.j; ++i) {
+                if (shard_ptrs) {  // {table index, address}
+                    pieces[2 * i] = job.stripe * static_cast<uint64_t>(c->n) + plan.entries[i].shard;
+                    pieces[2 * i + 1] = plan.entries[i].src;
+                    continue;
+                }
                 pieces[2 * i] = plan.entries[i].src;
                 pieces[2 * i + 1] = v.slot(job.stripe, plan.entries[i].shard, c->k);
             }
@@ -1234,11 +1245,16 @@ int update_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::UpdateP
     a.jobs = reinterpret_cast<const rsmi::UpdateJob*>(t.dev);
     a.entries = reinterpret_cast<const rsmi::UpdateEntry*>(t.dev + ent_off);
     hipError_t e = hipSuccess;
-    if (c->m > 0) e = rsmi::launch_update(a, plan.max_j, s);
+    if (c->m > 0)
+        e = shard_ptrs ? rsmi::launch_update_ptrs(a, shard_ptrs, shard_off, plan.max_j, s)
+                       : rsmi::launch_update(a, plan.max_j, s);
     // The pieces hold absolute addresses: offsets from a null base.
     if (e == hipSuccess && copy_commit)
-        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
-                                     static_cast<uint32_t>(count), v.span(), s);
+        e = shard_ptrs ? rsmi::launch_copy_table(shard_ptrs, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                                 static_cast<uint32_t>(count), v.span(), shard_off, true, s)
+                       : rsmi::launch_copy_pieces(nullptr, nullptr,
+                                                  reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                                  static_cast<uint32_t>(count), v.span(), s);
     if (e == hipSuccess) {
         c->update_stripes += static_cast<int64_t>(njobs);
         if (copy_commit) ++c->update_copy_commits;
@@ -1346,8 +1362,12 @@ enum class ReadFor { kRead, kScrub, kUpdate, kCrc };
 // job and entry tables, the jobs' pattern ids and the {src, dst} address pairs
 // of the wanted present shards go to the device in one upload (upload_tables);
 // then the read kernel, then the copies, on the same stream.
+// shard_ptrs: pointer mode (rs_read_ptrs; v is StripeView::ptrs).  The kernel's
+// twin resolves the survivors through the table, and the copies' pairs are
+// {table index, dst} for the table-resolving copy; shard_off is the byte
+// offset of the call's slice within every slot.
 int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan& plan, rsmi::ReadArgs a,
-                        hipStream_t s, ReadFor who) {
+                        hipStream_t s, ReadFor who, const uint64_t* shard_ptrs = nullptr, uint64_t shard_off = 0) {
     const size_t njobs = plan.jobs.size(), count = plan.entries.size(), ncopy = plan.copies.size();
     const size_t ent_off = njobs * sizeof(rsmi::ReadJob);
     const size_t pat_off = ent_off + count * sizeof(rsmi::ReadEntry);
@@ -1362,7 +1382,8 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::Re
         }
         uint64_t* pieces = reinterpret_cast<uint64_t*>(hb + pieces_off);
         for (size_t i = 0; i < ncopy; ++i) {
-            pieces[2 * i] = v.slot(plan.copies[i].stripe, plan.copies[i].shard, c->k);
+            pieces[2 * i] = shard_ptrs ? plan.copies[i].stripe * static_cast<uint64_t>(c->n) + plan.copies[i].shard
+                                       : v.slot(plan.copies[i].stripe, plan.copies[i].shard, c->k);
             pieces[2 * i + 1] = plan.copies[i].dst;
         }
     });
@@ -1374,12 +1395,15 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::Re
         a.jobs = reinterpret_cast<const rsmi::ReadJob*>(t.dev);
         a.entries = reinterpret_cast<const rsmi::ReadEntry*>(t.dev + ent_off);
         a.pats = reinterpret_cast<const uint32_t*>(t.dev + pat_off);
-        e = rsmi::launch_read(a, s);
+        e = shard_ptrs ? rsmi::launch_read_ptrs(a, shard_ptrs, shard_off, s) : rsmi::launch_read(a, s);
     }
     // The pieces hold absolute addresses: offsets from a null base.
     if (e == hipSuccess && ncopy > 0)
-        e = rsmi::launch_copy_pieces(nullptr, nullptr, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
-                                     static_cast<uint32_t>(ncopy), v.span(), s);
+        e = shard_ptrs ? rsmi::launch_copy_table(shard_ptrs, reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                                 static_cast<uint32_t>(ncopy), v.span(), shard_off, false, s)
+                       : rsmi::launch_copy_pieces(nullptr, nullptr,
+                                                  reinterpret_cast<const uint64_t*>(t.dev + pieces_off),
+                                                  static_cast<uint32_t>(ncopy), v.span(), s);
     if (e == hipSuccess && who == ReadFor::kScrub) {
         c->scrub_regenerated += static_cast<int64_t>(count);
     } else if (e == hipSuccess && who == ReadFor::kCrc) {
@@ -1398,9 +1422,10 @@ int launch_read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::Re
 // which count them in counters of their own, or old contents for rs_update_degraded (kUpdate), which
 // counts none.
 int read_stripes(rs_ctx* c, Lease& L, const StripeView& v, const rsmi::ReadPlan& plan, const rsmi::ReadArgs& a,
-                 hipStream_t s, ReadFor who = ReadFor::kRead) {
+                 hipStream_t s, ReadFor who = ReadFor::kRead, const uint64_t* shard_ptrs = nullptr,
+                 uint64_t shard_off = 0) {
     return with_patterns(c, L, plan.erased.data(), plan.jobs.size(), s,
-                         [&] { return launch_read_stripes(c, L, v, plan, a, s, who); });
+                         [&] { return launch_read_stripes(c, L, v, plan, a, s, who, shard_ptrs, shard_off); });
 }
 
 // ------------------------------------------------------- degraded verify ----
@@ -3465,6 +3490,9 @@ const char* rs_kernel_name(const rs_ctx* c, int which) {
     if (which == 17) return rsmi::column_lens_variant_name(c->m);
     if (which == 18) return rsmi::crc32c_variant_name();
     if (which == 19) return rsmi::crc32c_ptrs_variant_name();
+    if (which == 20 && c->bitslice) return c->bitslice->ptrs_name;
+    if (which == 21) return rsmi::update_ptrs_variant_name(c->m);
+    if (which == 22) return rsmi::read_ptrs_variant_name(c->k);
     if (which == 0 && c->bitslice) return c->bitslice->name;
     if (which == 1 && c->bitslice_rec) return c->rec_name.c_str();
     return rsmi::variant_name(c->k, c->m);
@@ -3987,6 +4015,82 @@ int rs_reconstruct_checked_ptrs_lens(rs_ctx* c, const uint64_t* shard_ptrs, cons
                                      const uint8_t* erased, uint32_t* first_bad, void* stream) {
     if (!c) return RS_EINVAL;
     return scrub_lens(c, shard_ptrs, lens, stripes, erased, first_bad, true, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// What rs_encode_ptrs, rs_update_ptrs and rs_read_ptrs refuse alike, behind
+// the NULL-ctx and nothing-to-do checks: the table, the slice (shard_off /
+// 16 plus the column count stays below 2^28: 32-bit column offsets) and the
+// stripe count (32-bit stripe indices, as the other _ptrs calls).
+bool check_ptrs_io_args(const uint64_t* shard_ptrs, size_t shard_off, size_t len, size_t stripes) {
+    if (!shard_ptrs || (reinterpret_cast<uintptr_t>(shard_ptrs) & 7u)) return false;
+    if (shard_off & 15u) return false;
+    if (shard_off / 16 + round_up(len, 16) / 16 >= (size_t(1) << 28)) return false;
+    return stripes <= 0xFFFFFFFFull;
+}
+}  // namespace
+
+int rs_encode_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (c->m == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!check_ptrs_io_args(shard_ptrs, 0, len, stripes)) return RS_EINVAL;
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    const StripeView v = StripeView::ptrs(round_up(len, 16), len);
+    // Reads only state that is immutable after rs_new: no lock, no lease.
+    DeviceGuard g(c->device);
+    if (!g.ok) return RS_EDEVICE;
+    if (c->bitslice) {
+        rsmi::BitslicePtrArgs b{};
+        b.shard_ptrs = shard_ptrs;
+        b.stripes = stripes;
+        b.ncols16 = v.ncols16();
+        b.blocks_per_stripe = (b.ncols16 + 511u) / 512u;  // as launch_encode
+        b.xcd = c->xcd;
+        if (b.stripes * b.blocks_per_stripe > 0x7FFFFFFFull) return RS_EINVAL;
+        return hip_status(c->bitslice->ptrs_launch(b, static_cast<hipStream_t>(stream)));
+    }
+    if (rsmi::matmul_blocks(c->k, c->m, v.ncols16(), stripes) > 0x7FFFFFFFull) return RS_EINVAL;
+    rsmi::MatArgs a = base_args(c, v, stripes);
+    set_patterns(c, 1, c->d_encpat.p, a);
+    a.stripe_desc = nullptr;
+    a.shard_ptrs = shard_ptrs;
+    a.xcd = c->xcd_split_enc;
+    return hip_status(rsmi::launch_matmul(a, c->m, static_cast<hipStream_t>(stream)));
+}
+
+int rs_update_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t shard_off, size_t len, size_t stripes,
+                   const rs_shard_update* updates, size_t count, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!updates) return RS_EINVAL;
+    if (!check_ptrs_io_args(shard_ptrs, shard_off, len, stripes)) return RS_EINVAL;
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    rsmi::UpdatePlan plan;
+    const int rc = rsmi::plan_updates(c->k, stripes, updates, count, &plan);
+    if (rc != RS_OK) return rc;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return update_stripes(c, *sc.L, StripeView::ptrs(round_up(len, 16), len), plan, static_cast<hipStream_t>(stream),
+                          shard_ptrs, shard_off);
+}
+
+int rs_read_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t shard_off, size_t len, size_t stripes,
+                 const uint8_t* erased, const rs_shard_read* reads, size_t count, void* stream) {
+    if (!c) return RS_EINVAL;
+    if (count == 0 || stripes == 0 || len == 0) return RS_OK;
+    if (!erased || !reads) return RS_EINVAL;
+    if (!check_ptrs_io_args(shard_ptrs, shard_off, len, stripes)) return RS_EINVAL;
+    if (!route(c, shard_ptrs)) return RS_EINVAL;
+    const StripeView v = StripeView::ptrs(round_up(len, 16), len);
+    rsmi::ReadPlan plan;
+    const int rc = rsmi::plan_reads(c->k, c->n, stripes, erased, v.span(), reads, count, &plan);
+    if (rc != RS_OK) return rc;
+    rsmi::ReadArgs a = read_args(c, v, plan.jobs.size());
+    if (!rsmi::plan_read(&a, plan.max_j)) return RS_EINVAL;
+    if (!copy_pieces_fit(plan.copies.size(), a.ncols16)) return RS_EINVAL;
+    CallScope sc(c);
+    if (sc.error() != RS_OK) return sc.error();
+    return read_stripes(c, *sc.L, v, plan, a, static_cast<hipStream_t>(stream), ReadFor::kRead, shard_ptrs, shard_off);
 }
 
 int rs_correct_columns_ptrs(rs_ctx* c, const uint64_t* shard_ptrs, size_t len, size_t stripes, const uint8_t* erased,

@@ -39,6 +39,7 @@ EXPORTS = (
     "rs_encode_matrix", "rs_strerror", "rs_encode", "rs_decode", "rs_decode_batch", "rs_encode_batch",
     "rs_encode_stripes", "rs_reconstruct_stripes", "rs_reconstruct_ptrs", "rs_pattern_count",
     "rs_verify_ptrs", "rs_correct_columns_ptrs",
+    "rs_encode_ptrs", "rs_update_ptrs", "rs_read_ptrs",
     "rs_reconstruct_checked", "rs_reconstruct_checked_ptrs",
     "rs_verify_ptrs_lens", "rs_reconstruct_checked_ptrs_lens", "rs_correct_columns_ptrs_lens",
     "rs_verify_stripes", "rs_correct_stripes", "rs_update_stripes", "rs_read_stripes",
@@ -168,6 +169,9 @@ def _lib() -> ctypes.CDLL:
             "rs_reconstruct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_reconstruct_ptrs": (i32, [vp, vp, sz, sz, vp, vp]),
             "rs_verify_ptrs": (i32, [vp, vp, sz, sz, vp, vp, vp]),
+            "rs_encode_ptrs": (i32, [vp, vp, sz, sz, vp]),
+            "rs_update_ptrs": (i32, [vp, vp, sz, sz, sz, ctypes.POINTER(ShardUpdate), sz, vp]),
+            "rs_read_ptrs": (i32, [vp, vp, sz, sz, sz, vp, ctypes.POINTER(ShardRead), sz, vp]),
             "rs_correct_columns_ptrs": (i32, [vp, vp, sz, sz, vp, ctypes.POINTER(i32), vp, vp]),
             "rs_verify_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, vp, vp]),
             "rs_correct_stripes": (i32, [vp, vp, sz, vp, sz, sz, sz, sz, ctypes.POINTER(i32), vp, vp]),
@@ -364,7 +368,8 @@ class FEC:
         repair (verify_ptrs_lens, reconstruct_checked_ptrs_lens), 17 the
         per-job-length twin of the pointer-mode column kernel
         (correct_columns_ptrs_lens), 18 and 19 the sector-checksum kernel
-        (crc32c_*) and its pointer-mode twin: diagnostics."""
+        (crc32c_*) and its pointer-mode twin, 20 to 22 the kernels serving
+        encode_ptrs, update_ptrs and read_ptrs: diagnostics."""
         return _lib().rs_kernel_name(self._h, which).decode()
 
     def matrix(self) -> bytes:
@@ -820,6 +825,44 @@ class FEC:
         _check(_lib().rs_verify_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes,
                                      ctypes.cast(buf, ctypes.c_void_p), first_bad_ptr or None, stream or None),
                "rs_verify_ptrs")
+
+    def encode_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, stream: int = 0) -> None:
+        """rs_encode_ptrs: encode_stripes for shards at the device addresses
+        in the device array shard_ptrs_dev[s * n + i], as reconstruct_ptrs:
+        the m parity slots of every stripe are written from its k data slots.
+        Enqueued on stream."""
+        _check(_lib().rs_encode_ptrs(self._h, shard_ptrs_dev or None, shard_len, stripes, stream or None),
+               "rs_encode_ptrs")
+
+    def update_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, updates: Sequence[tuple],
+                    offset: int = 0, stream: int = 0) -> None:
+        """rs_update_ptrs: update_stripes for shards at the device addresses
+        in shard_ptrs_dev[s * n + i].  updates as there; bytes [offset,
+        offset + shard_len) of the changed shards' slots take the contents at
+        src_ptr and the same bytes of the stripe's parity slots are patched.
+        Only the table entries of the changed shards and of the parity of
+        listed stripes are dereferenced.  Enqueued on stream."""
+        arr = updates if isinstance(updates, ctypes.Array) else shard_updates(updates)
+        _check(_lib().rs_update_ptrs(self._h, shard_ptrs_dev or None, offset, shard_len, stripes, arr,
+                                     len(updates), stream or None), "rs_update_ptrs")
+
+    def read_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: Optional[bytes],
+                  reads: Sequence[tuple], offset: int = 0, stream: int = 0) -> None:
+        """rs_read_ptrs: read_stripes for shards at the device addresses in
+        shard_ptrs_dev[s * n + i].  reads as there; dst_ptr receives bytes
+        [offset, offset + shard_len) of the shard, copied or computed from the
+        stripe's survivors.  Nothing the table names is written and entries of
+        erased shards are never dereferenced.  erased None is passed on as
+        NULL, which the call refuses.  Enqueued on stream."""
+        buf = None
+        if erased is not None:
+            if len(erased) != stripes * self.n:
+                raise RSError(RS_EINVAL, "erased must hold stripes*n flags")
+            buf = ctypes.c_char_p(bytes(erased))
+        arr = reads if isinstance(reads, ctypes.Array) else shard_reads(reads)
+        _check(_lib().rs_read_ptrs(self._h, shard_ptrs_dev or None, offset, shard_len, stripes,
+                                   ctypes.cast(buf, ctypes.c_void_p), arr, len(reads), stream or None),
+               "rs_read_ptrs")
 
     def reconstruct_checked_ptrs(self, shard_ptrs_dev: int, shard_len: int, stripes: int, erased: bytes,
                                  first_bad_ptr: int, stream: int = 0) -> None:
