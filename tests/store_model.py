@@ -18,8 +18,13 @@ the next comparison so that every later "untouched" check stays strict.
 Everything else is compared exactly at every checkpoint: guards, pitch
 padding, stride gaps, decoy rows, erased slots after a garbage fill, the
 first_bad rows, and in pointer mode the address table.
+
+The Model also has the scattered-shard I/O calls, the calls with a length per
+stripe and the sector checksums; the scenarios that use them, and the driver
+that overrides this one's call_* hooks for them, are in store_model_io.py.
 """
 import collections
+import ctypes
 
 import numpy as np
 
@@ -82,6 +87,58 @@ def survivors(er_row, k, n):
     return ids if int(np.sum(np.asarray(er_row) != 0)) <= n - k else None
 
 
+def _crc_table():
+    t = np.arange(256, dtype=np.uint32)
+    for _ in range(8):
+        t = np.where(t & 1, (t >> 1) ^ np.uint32(0x82F63B78), t >> 1).astype(np.uint32)
+    return t
+
+
+_CRC_TABLE = _crc_table()
+_CRC_MEMO = {}
+
+
+def crc32c_rows(rows, lens=None):
+    """CRC-32C as RFC 3720 defines it (reflected polynomial 0x82F63B78, initial
+    value 0xFFFFFFFF, final XOR 0xFFFFFFFF), byte by byte through the table,
+    of the first lens[r] bytes of every row of `rows` [N][W] at once."""
+    rows = np.asarray(rows, dtype=np.uint8)
+    lens = np.full(len(rows), rows.shape[1]) if lens is None else np.asarray(lens)
+    c = np.full(len(rows), 0xFFFFFFFF, dtype=np.uint32)
+    for j in range(int(lens.max(initial=0))):
+        nxt = _CRC_TABLE[(c ^ rows[:, j]) & 0xFF] ^ (c >> 8)
+        c = np.where(j < lens, nxt, c)
+    return c ^ np.uint32(0xFFFFFFFF)
+
+
+def crc32c(message):
+    return int(crc32c_rows(np.frombuffer(bytes(message), dtype=np.uint8)[None, :])[0])
+
+
+def crc32c_sectors(shards, sector):
+    """The checksums of the ceil(S / sector) sectors of every shard of a list
+    of equally long shards, the last sector over what is left: [uint32[nsec]].
+    All sectors go through the table side by side; a shard's result is
+    remembered by its content (most shards do not change between two calls)."""
+    keys = [(bytes(x), sector) for x in shards]
+    out = {key: _CRC_MEMO[key] for key in keys if key in _CRC_MEMO}
+    todo = list(dict.fromkeys(key for key in keys if key not in out))
+    if todo:
+        if len(_CRC_MEMO) > 2048:
+            _CRC_MEMO.clear()
+        S = len(todo[0][0])
+        nsec, W = -(-S // sector), min(sector, S)
+        rows = np.zeros((len(todo) * nsec, W), dtype=np.uint8)
+        for r, (content, _) in enumerate(todo):
+            for j in range(nsec):
+                part = np.frombuffer(content, dtype=np.uint8)[j * sector:(j + 1) * sector]
+                rows[r * nsec + j, :len(part)] = part
+        sums = crc32c_rows(rows, [min(sector, S - j * sector) for j in range(nsec)] * len(todo))
+        for r, key in enumerate(todo):
+            _CRC_MEMO[key] = out[key] = sums[r * nsec:(r + 1) * nsec]
+    return [out[key] for key in keys]
+
+
 class HostEngine:
     """What the Model and the naive engine of test_store_model.py share: the
     Memory and the host-side writes of the driver.  No addressing, no flag
@@ -115,6 +172,7 @@ class Model(HostEngine):
         super().__init__(k, n, mem)
         self.E = oracle.fec_matrix(k, n)
         self._D = {}
+        self.beyond = False     # columns beyond the decoding radius are expected (_codeword)
 
     # ---- addressing ----------------------------------------------------------
     def strided(self, data, dss, parity, pss, pitch):
@@ -181,24 +239,50 @@ class Model(HostEngine):
         cols = np.flatnonzero(bad)
         return (int(cols[0]) if cols.size else CLEAN), cols
 
-    def _codeword(self, slot, s, er_row, S, cols):
+    def _codeword(self, slot, s, er_row, S, cols, failed=None):
         """rs_correct_columns: "a codeword lies within Hamming distance
         floor((r - k) / 2) of y: it is unique".  The oracle's Correct over the
         columns `cols` of the present shards; (present ids, their codeword
         bytes at those columns).  The model is given no column beyond the
-        radius ("may ... land on another codeword")."""
+        radius ("may ... land on another codeword"), unless the caller passes
+        a list for them: then "a column beyond the radius ... is left alone
+        while the others are corrected", the oracle deciding column by column
+        which those are, and their positions in cols are appended to it
+        (_columns does so only while `beyond` is set, which the one step that
+        damages a stripe past the radius on purpose does: anywhere else such a
+        column is a damage plan gone wrong and is reported as that)."""
         pres = [i for i in range(self.n) if not er_row[i]]
         t = (len(pres) - self.k) // 2
         y = np.stack([self.mem.view(slot(s, i), S)[cols] for i in pres])
-        word, todo, suspects = np.empty_like(y), np.arange(len(cols)), set()
+        word, todo, suspects, tried, step = np.empty_like(y), np.arange(len(cols)), set(), None, 8
         while todo.size:
             # the oracle's Berlekamp-Welch, a few columns at a time ...
-            head, todo = todo[:8], todo[8:]
-            rc, data = oracle.decode_correct(self.E, self.k, self.n,
-                                             [(i, y[j, head].tobytes()) for j, i in enumerate(pres)])
-            assert rc == 0, ("the model was given a column beyond the decoding radius", rc)
+            head, todo = todo[:step], todo[step:]
+            rc, data = (1, None) if step > 8 else oracle.decode_correct(
+                self.E, self.k, self.n, [(i, y[j, head].tobytes()) for j, i in enumerate(pres)])
+            if rc != 0 and failed is not None:
+                data = np.zeros((self.k, len(head)), dtype=np.uint8)
+                lost = []
+                for q, c in enumerate(head):     # one of them is beyond the radius: which
+                    rc1, d1 = self._decode_column(pres, y[:, c])
+                    if rc1 != 0:
+                        lost.append(q)
+                    else:
+                        data[:, q] = d1
+                step = 64 if len(lost) == len(head) else 8   # a run of them: no more calls for eight at once
+                if step == 64:
+                    word[:, head] = y[:, head]
+                    failed += [int(c) for c in head]
+                    continue
+                data = data.tobytes()
+            else:
+                assert rc == 0, ("the model was given a column beyond the decoding radius", rc)
+                lost = []
             d = np.frombuffer(data, dtype=np.uint8).reshape(self.k, len(head))
             word[:, head] = np.stack(oracle.matmul_stripe(np.ascontiguousarray(self.E[pres]), [r.copy() for r in d]))
+            if lost:
+                word[:, head[lost]] = y[:, head[lost]]
+                failed += [int(c) for c in head[lost]]
             suspects |= {j for j in range(len(pres)) if (word[j, head] != y[j, head]).any()}
             good = [j for j in range(len(pres)) if j not in suspects][:self.k]
             if not todo.size or len(good) < self.k:
@@ -207,6 +291,9 @@ class Model(HostEngine):
             # so far, wherever it lies within the radius: there it is the
             # unique one.  The columns where it does not go round again.
             key = tuple(pres[j] for j in good) + (-1,) + tuple(pres)
+            if key == tried:    # the columns left have been held against this codeword already
+                continue
+            tried = key
             if key not in self._D:
                 self._D[key] = np_rs.matmul(self.E[pres], np_rs.invert(self.E[[pres[j] for j in good]]))
             cand = np.stack(oracle.matmul_stripe(self._D[key], [y[j, todo].copy() for j in good]))
@@ -214,6 +301,21 @@ class Model(HostEngine):
             word[:, todo[ok]] = cand[:, ok]
             todo = todo[~ok]
         return pres, word
+
+    def _decode_column(self, pres, column):
+        """oracle.decode_correct for one column of the shards pres, through
+        call arrays that are built once per set of present shards."""
+        key = ("column",) + tuple(pres)
+        if key not in self._D:
+            col, out = np.empty(len(pres), dtype=np.uint8), np.zeros(self.k, dtype=np.uint8)
+            nums = (ctypes.c_int * len(pres))(*pres)
+            ptrs = (ctypes.c_void_p * len(pres))(*[col.ctypes.data + j for j in range(len(pres))])
+            self._D[key] = (col, out, nums, ptrs, np.ascontiguousarray(self.E))
+        col, out, nums, ptrs, E = self._D[key]
+        col[:] = column
+        rc = oracle.lib().orc_decode_correct(E.ctypes.data, self.k, self.n, ctypes.addressof(nums),
+                                             ctypes.addressof(ptrs), len(pres), 1, out.ctypes.data)
+        return rc, out.copy()
 
     def _fb(self, first_bad, stripes):
         return self.mem.view(first_bad, 4 * stripes).view(np.uint32)
@@ -307,7 +409,10 @@ class Model(HostEngine):
             if self.m - int((er[s] != 0).sum()) < 2:
                 status[s] = RS_ETOO_MANY_ERRORS
                 continue
-            pres, word = self._codeword(slot, s, er[s], S, cols)
+            failed = [] if self.beyond else None
+            pres, word = self._codeword(slot, s, er[s], S, cols, failed)
+            if failed:
+                status[s] = RS_ETOO_MANY_ERRORS
             for i, w in zip(pres, word):
                 stored = self.mem.view(slot(s, i), S)
                 diff = stored[cols] != w
@@ -370,7 +475,10 @@ class Model(HostEngine):
         holds "round_up(shard_len, 16) readable bytes, all of which are coded
         and committed"; "A listed stripe with more than m erasures whose
         changed shards are all present is served"."""
-        slot, er, R = self.strided(data, dss, parity, pss, pitch), self.flags(erased, stripes), r16(S)
+        self._update(self.strided(data, dss, parity, pss, pitch), S, self.flags(erased, stripes), updates)
+
+    def _update(self, slot, S, er, updates):
+        R = r16(S)
         by = collections.OrderedDict()
         for s, c, src in updates:
             by.setdefault(int(s), []).append((int(c), src))
@@ -405,7 +513,10 @@ class Model(HostEngine):
         from the k survivors Rebuild chooses for the stripe's erasure set";
         "round_up(shard_len, 16) bytes of dst are written; those past
         shard_len are unspecified"."""
-        slot, er, R = self.strided(data, dss, parity, pss, pitch), self.flags(erased, stripes), r16(S)
+        self._read(self.strided(data, dss, parity, pss, pitch), S, self.flags(erased, stripes), reads)
+
+    def _read(self, slot, S, er, reads):
+        R = r16(S)
         for s, i, _ in reads:
             if er[s, i]:
                 self._enough(er, [s])
@@ -450,10 +561,184 @@ class Model(HostEngine):
             raise Refused(RS_ENOT_ENOUGH)
         return ids
 
+    # ---- scattered-shard I/O -----------------------------------------------------
+    def encode_ptrs(self, tab, S, stripes):
+        """"rs_encode_ptrs is rs_encode_stripes on that placement: parity shard
+        r of stripe s is written at shard_ptrs[s * n + k + r], and its
+        round_up(shard_len, 16) bytes are bit for bit what rs_encode_stripes
+        writes for the same data"; "m == 0: RS_OK"."""
+        if self.m and S:
+            self._encode(self.table(tab, stripes), S, stripes)
+
+    def update_ptrs(self, tab, S, stripes, updates, offset=0):
+        """"the call works on bytes [shard_offset, shard_offset + shard_len) of
+        every slot it touches, and src holds the slice's new bytes from its
+        start"; "Only the table entries of a listed stripe's changed shards
+        and of its m parity shards are loaded" (the table is read entry by
+        entry, as each is needed)."""
+        at = self.table(tab, stripes)
+        self._update(lambda s, i: at(s, i) + offset, S, self.flags(None, stripes), updates)
+
+    def read_ptrs(self, tab, S, stripes, erased, reads, offset=0):
+        """"A present wanted shard is copied; an erased one is computed from
+        the k survivors Rebuild chooses"; "Nothing named by the table is
+        written, and the table entries of erased shards are never loaded";
+        "bytes [shard_offset, shard_offset + shard_len) of the slots are read
+        and dst receives the slice from its start"."""
+        at = self.table(tab, stripes)
+        self._read(lambda s, i: at(s, i) + offset, S, self.flags(erased, stripes), reads)
+
+    # ---- a length per stripe -----------------------------------------------------
+    def _each(self, tab, shard_lens, stripes, erased):
+        """"Stripe s is treated exactly as the equal-length call would treat it
+        if it were called on that stripe alone with shard_len = shard_lens[s]";
+        "RS_ENOT_ENOUGH when any stripe has more than m erasures", a stripe
+        without bytes included, before anything is written.  The lengths are
+        copied at once: "is not retained".  Yields (s, its length, its slot
+        function as stripe 0, its flags)."""
+        lens, er, at = [int(x) for x in shard_lens], self.flags(erased, stripes), self.table(tab, stripes)
+        assert len(lens) == stripes
+        self._enough(er)
+        return [(s, lens[s], (lambda s: lambda _, i: at(s, i))(s), er[s:s + 1]) for s in range(stripes)]
+
+    def verify_ptrs_lens(self, tab, shard_lens, stripes, first_bad, erased=None):
+        """"a stripe with shard_lens[s] == 0 ... reads nothing, writes nothing,
+        gets RS_VERIFY_CLEAN"; "RS_OK with nothing written for stripes == 0 or
+        when every length is 0"."""
+        each = self._each(tab, shard_lens, stripes, erased)
+        if not any(L for _, L, _, _ in each):
+            return
+        for s, L, slot, er in each:
+            if L:
+                self._verify(slot, L, 1, er, first_bad + 4 * s)
+            else:
+                self._fb(first_bad + 4 * s, 1)[0] = CLEAN
+
+    def reconstruct_checked_ptrs_lens(self, tab, shard_lens, stripes, erased, first_bad):
+        each = self._each(tab, shard_lens, stripes, erased)
+        if not any(L for _, L, _, _ in each):
+            return
+        for s, L, slot, er in each:
+            if L:
+                self._reconstruct(slot, L, 1, er, first_bad + 4 * s)
+            else:
+                self._fb(first_bad + 4 * s, 1)[0] = CLEAN
+
+    def correct_columns_ptrs_lens(self, tab, shard_lens, stripes, erased=None):
+        """"m > 16" -> RS_EINVAL; "a stripe with shard_lens[s] == 0 ... ends
+        RS_OK with zero corrected"."""
+        each = self._each(tab, shard_lens, stripes, erased)
+        status, corrected = [RS_OK] * stripes, [0] * (stripes * self.n)
+        if self.m == 0 or not any(L for _, L, _, _ in each):
+            return status, corrected
+        if self.m > 16:
+            raise Refused(RS_EINVAL)
+        for s, L, slot, er in each:
+            if L:
+                st, co = self._columns(slot, L, 1, er)
+                status[s], corrected[s * self.n:(s + 1) * self.n] = st[0], co
+        return status, corrected
+
+    # ---- sector checksums --------------------------------------------------------
+    def _sums(self, slot, S, stripes, er, sector):
+        """"the checksum of sector j covers the bytes [j * sector_len, min((j +
+        1) * sector_len, shard_len)) and nothing else -- never the padding up
+        to 16 or the pitch gap"; "The slots of erased shards are never
+        dereferenced".  {(s, i): uint32[nsec]} of the present shards."""
+        ids = [(s, i) for s in range(stripes) for i in range(self.n) if not er[s, i]]
+        return dict(zip(ids, crc32c_sectors([self.mem.view(slot(s, i), S) for s, i in ids], sector)))
+
+    def _crcs(self, crcs, stripes, crc_pitch):
+        return self.mem.view(crcs, 4 * stripes * self.n * crc_pitch).view(np.uint32).reshape(stripes * self.n, crc_pitch)
+
+    def _crc_store(self, slot, S, stripes, er, sector, crcs, crc_pitch):
+        """"computes and stores the checksums of every present shard; the
+        entries of erased shards are left as they are"; "entries between nsec
+        and crc_pitch are never read or written"."""
+        if S == 0 or stripes == 0:
+            return
+        tab = self._crcs(crcs, stripes, crc_pitch)
+        for (s, i), c in self._sums(slot, S, stripes, er, sector).items():
+            tab[s * self.n + i, :len(c)] = c
+
+    def _crc_check(self, slot, S, stripes, er, sector, crcs, crc_pitch, first_bad):
+        """"first_bad ... gets, at [s * n + i], the lowest sector index of
+        shard i of stripe s whose bytes do not match the stored checksum, or
+        RS_VERIFY_CLEAN; an erased shard gets RS_VERIFY_CLEAN.  Writes nothing
+        but first_bad"."""
+        if S == 0 or stripes == 0:
+            return
+        tab, fb = self._crcs(crcs, stripes, crc_pitch), self._fb(first_bad, stripes * self.n)
+        fb[:] = CLEAN
+        for (s, i), c in self._sums(slot, S, stripes, er, sector).items():
+            bad = np.flatnonzero(tab[s * self.n + i, :len(c)] != c)
+            if bad.size:
+                fb[s * self.n + i] = int(bad[0])
+
+    def crc32c_stripes(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, erased=None):
+        self._crc_store(self.strided(data, dss, parity, pss, pitch), S, stripes, self.flags(erased, stripes), sector,
+                        crcs, crc_pitch)
+
+    def crc32c_ptrs(self, tab, S, stripes, sector, crcs, crc_pitch, erased=None):
+        self._crc_store(self.table(tab, stripes), S, stripes, self.flags(erased, stripes), sector, crcs, crc_pitch)
+
+    def crc32c_check_stripes(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, first_bad,
+                             erased=None):
+        self._crc_check(self.strided(data, dss, parity, pss, pitch), S, stripes, self.flags(erased, stripes), sector,
+                        crcs, crc_pitch, first_bad)
+
+    def crc32c_check_ptrs(self, tab, S, stripes, sector, crcs, crc_pitch, first_bad, erased=None):
+        self._crc_check(self.table(tab, stripes), S, stripes, self.flags(erased, stripes), sector, crcs, crc_pitch,
+                        first_bad)
+
+    def correct_crc32c(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, erased=None):
+        """The header's steps: "1. every present shard is checked; B(s) is the
+        set of present shards of stripe s with a mismatching sector, X(s) its
+        erased shards; 2. B empty: the stripe is RS_OK and untouched (a clean
+        stripe with more than m erasures too); 3. |X + B| > m: the stripe is
+        RS_ETOO_MANY_ERRORS and nothing in it is written; 4. otherwise every
+        shard of B is regenerated in place, whole, from the k survivors
+        Rebuild chooses for X + B ...; the slots of X are neither read nor
+        written; 5. the regenerated shards are checked against their stored
+        checksums again ...; one that still mismatches makes its stripe
+        RS_ETOO_MANY_ERRORS".  "RS_ENOT_ENOUGH, with nothing written, when a
+        stripe with more than m erasures also has a mismatch.  Checksums are
+        never written by this call"."""
+        slot, er = self.strided(data, dss, parity, pss, pitch), self.flags(erased, stripes)
+        status, rewritten = [RS_OK] * stripes, bytearray(stripes * self.n)
+        if S == 0 or stripes == 0:
+            return status, bytes(rewritten)
+        tab, R = self._crcs(crcs, stripes, crc_pitch), r16(S)
+        B = [[] for _ in range(stripes)]
+        for (s, i), c in self._sums(slot, S, stripes, er, sector).items():
+            if (tab[s * self.n + i, :len(c)] != c).any():
+                B[s].append(i)
+        for s in range(stripes):
+            if B[s] and int((er[s] != 0).sum()) > self.m:
+                raise Refused(RS_ENOT_ENOUGH)
+        for s in range(stripes):
+            if not B[s]:
+                continue
+            known = er[s].copy()
+            known[B[s]] = 1
+            if int((known != 0).sum()) > self.m:
+                status[s] = RS_ETOO_MANY_ERRORS
+                continue
+            ids, D = self.decode_matrix(known)
+            for i, v in zip(B[s], self._apply(D, B[s], slot, s, ids, R)):
+                self.mem.view(slot(s, i), R)[:] = v
+                self.mem.wrote(slot(s, i), S)
+                rewritten[s * self.n + i] = 1
+                c = crc32c_sectors([v[:S]], sector)[0]
+                if (tab[s * self.n + i, :len(c)] != c).any():
+                    status[s] = RS_ETOO_MANY_ERRORS
+        return status, bytes(rewritten)
+
 
 # =============================================================================
 # The scenario: geometry, driver, ledger
 # =============================================================================
+PTRS = ("ptrs", "ptrs_io", "ptrs_lens")      # the placements with an address table
 KINDS = ("update", "update_degraded", "read", "lose", "damage", "verify", "checked", "columns", "shards",
          "reconstruct")
 NROWS = 64        # rows of the source / destination pool
@@ -489,7 +774,7 @@ class Scene:
 
     def __init__(self, k, n, S, stripes, placement, seed):
         self.k, self.n, self.S, self.stripes, self.placement = k, n, S, stripes, placement
-        self.ptrs = placement == "ptrs"
+        self.ptrs = placement in PTRS
         self.G = Pool(k, n, S, stripes, seed) if self.ptrs else Layout(k, n, S, stripes, seed, placement)
         self.pitch = r16(S) + 32
         rng = np.random.default_rng(seed + 77)
@@ -558,8 +843,9 @@ class Driver:
         assert gran in ("every", "async")
         self.k, self.n, self.m, self.S, self.stripes = k, n, n - k, S, stripes
         self.placement, self.seed, self.gran, self.walk = placement, seed, gran, walk
-        self.scene = Scene(k, n, S, stripes, placement, seed)
+        self.scene = self.make_scene()
         self.ptrs = self.scene.ptrs
+        self.L = self.lengths()
         self.model = Model(k, n, Memory(self.scene.names, self.scene.init))
         self.engine = make_engine(k, n, self.scene.names, self.scene.init)
         self.rng = np.random.default_rng(seed)
@@ -571,8 +857,18 @@ class Driver:
         if self.ptrs:
             for e in (self.model, self.engine):
                 e.poke(self.scene.TAB, 0, self.scene.table_bytes(e.bases))
+                if hasattr(self.scene, "TABIO"):
+                    e.poke(self.scene.TABIO, 0, self.scene.table_bytes(e.bases))
 
     # ---- plumbing --------------------------------------------------------------
+    def make_scene(self):
+        return Scene(self.k, self.n, self.S, self.stripes, self.placement, self.seed)
+
+    def lengths(self):
+        """The shard length of every stripe: S, but for the placement with a
+        length per stripe."""
+        return [self.S] * self.stripes
+
     def what(self):
         return (f"seed {self.seed} RS({self.k},{self.n}) S={self.S} x{self.stripes} {self.placement} "
                 f"{self.gran}, op {self.op} {self.opname}")
@@ -582,6 +878,7 @@ class Driver:
         the code it is refused with) is compared at once."""
         self.op += 1
         self.opname = name
+        self.ledger["call " + name] += 1
         res = []
         for e in (self.model, self.engine):
             try:
@@ -608,12 +905,14 @@ class Driver:
             if name == "table":
                 assert np.array_equal(w, self.scene.table_bytes(self.model.bases))
                 w = self.scene.table_bytes(self.engine.bases)
+            if name == "table_io":      # addresses in the pool: compared as offsets into it
+                w = (w.view(np.int64) - self.model.bases[0] + self.engine.bases[0]).view(np.uint8)
             bad = np.flatnonzero((g != w) & ~lo)
             if bad.size:
                 first = [(int(o), self.scene.where(name, int(o)), int(g[o]), int(w[o])) for o in bad[:8]]
                 raise Mismatch(f"{self.what()}: buffer {name}: {bad.size} bytes differ; "
                                f"(offset, where, engine, model) {first}")
-            if name != "table":
+            if name not in ("table", "table_io"):
                 w[lo] = g[lo]
                 lo[:] = False
 
@@ -655,10 +954,10 @@ class Driver:
 
     def wrong(self, s, er_row=None):
         er_row = self.er[s] if er_row is None else er_row
-        w = np.zeros((self.n, self.S), dtype=bool)
+        w, L = np.zeros((self.n, self.S), dtype=bool), self.L[s]
         for i in range(self.n):
             if not er_row[i]:
-                w[i] = self.stored(s, i) != self.truth[s, i]
+                w[i, :L] = self.stored(s, i)[:L] != self.truth[s, i, :L]
         return w
 
     def clean(self, s):
@@ -684,6 +983,9 @@ class Driver:
     def op_encode(self):
         if self.m == 0:
             return
+        self.call_encode()
+
+    def call_encode(self):
         if not self.ptrs:
             self.both("encode_stripes", lambda e: e.encode_stripes(*self.sargs(e)))
             return
@@ -694,7 +996,13 @@ class Driver:
 
     def op_verify(self, er=None):
         er = self.er if er is None else er
-        off, fl = self.fbrow(), er.tobytes()
+        off = self.fbrow()
+        self.call_verify(er, off)
+        self.ledger["verify"] += 1
+        return self.verdicts(off)
+
+    def call_verify(self, er, off):
+        fl = er.tobytes()
         if self.ptrs:
             self.both("verify_ptrs", lambda e: e.verify_ptrs(*self.targs(e), e.adr(self.scene.FB, off),
                                                              erased=fl if er.any() else None))
@@ -702,8 +1010,6 @@ class Driver:
             self.both("verify_degraded", lambda e: e.verify_degraded(*self.sargs(e), fl, e.adr(self.scene.FB, off)))
         else:
             self.both("verify_stripes", lambda e: e.verify_stripes(*self.sargs(e), e.adr(self.scene.FB, off)))
-        self.ledger["verify"] += 1
-        return self.verdicts(off)
 
     def fresh_rows(self, count):
         offs = self.rows(count)
@@ -711,13 +1017,14 @@ class Driver:
             self.host("poke", self.scene.ROWS, o, self.rng.integers(0, 256, size=r16(self.S), dtype=np.uint8))
         return offs
 
-    def slice_of(self):
+    def slice_of(self, S=None):
         """(o, l) of a slice: o = 16, l up to the shard's end or a multiple of 16."""
-        if self.S <= 16:
+        S = self.S if S is None else S
+        if S <= 16:
             return None
-        if self.S < 48 or self.rng.integers(2):
-            return 16, self.S - 16
-        return 16, 16 * int(self.rng.integers(1, (self.S - 16) // 16 + 1))
+        if S < 48 or self.rng.integers(2):
+            return 16, S - 16
+        return 16, 16 * int(self.rng.integers(1, (S - 16) // 16 + 1))
 
     def op_update(self, listed, sl=None, er=None):
         """listed: {stripe: [data shards]}; er: the flags of a degraded update."""
@@ -727,6 +1034,20 @@ class Driver:
             return False
         offs = self.fresh_rows(len(ups))
         kind = "update" if er is None else "update_degraded"
+        R = self.scene.ROWS
+        self.call_update(listed, ups, offs, o, l, er)
+        for (s, c), off in zip(ups, offs):
+            ll = min(l, self.L[s] - o)
+            self.truth[s, c, o:o + ll] = self.model.mem.bufs[R][off:off + ll]
+        for s in listed:
+            self.retruth(s)
+        self.ledger[kind] += 1
+        if er is not None:
+            self.ledger["absorbed"] += sum(int(er[s, c]) for s, c in ups)
+            self.ledger["over_m"] += sum(int(er[s].sum()) > self.m for s in listed)
+        return True
+
+    def call_update(self, listed, ups, offs, o, l, er):
         fl = None if er is None else er.tobytes()
         R = self.scene.ROWS
         if not self.ptrs:
@@ -738,15 +1059,6 @@ class Driver:
             self.both("update_stripes" if er is None else "update_degraded", call)
         else:
             self.update_by_combine(listed, dict(zip(ups, offs)), o, l, self.er if er is None else er)
-        for (s, c), off in zip(ups, offs):
-            self.truth[s, c, o:o + l] = self.model.mem.bufs[R][off:off + l]
-        for s in listed:
-            self.retruth(s)
-        self.ledger[kind] += 1
-        if er is not None:
-            self.ledger["absorbed"] += sum(int(er[s, c]) for s, c in ups)
-            self.ledger["over_m"] += sum(int(er[s].sum()) > self.m for s in listed)
-        return True
 
     def update_by_combine(self, listed, src, o, l, er):
         """The pointer placement has no update call: rs_combine's "data holder
@@ -754,20 +1066,28 @@ class Driver:
         E[k + r][shard] * (old ^ new) and the parity holder accumulates them",
         the old contents of an erased changed shard coming from its decode row
         (rs_pattern_rows, rs_pattern_survivors) first."""
-        R, E = self.scene.ROWS, self.model.E
         gone = [(s, c) for s, cs in listed.items() for c in cs if er[s, c]]
         tmp = dict(zip(gone, self.rows(len(gone))))
         if gone:
-            def regen(e):
-                jobs = []
-                for s, c in gone:
-                    rows, cnt = e.pattern_rows(er[s].tobytes())
-                    ids = e.pattern_survivors(er[s].tobytes())
-                    rk = int(er[s, :c].sum())
-                    jobs.append(([self.slot(e, s, i, o) for i in ids], [e.adr(R, tmp[(s, c)])],
-                                 rows[rk * self.k:(rk + 1) * self.k], 0))
-                return e.combine(jobs, l)
-            self.both("combine(old contents)", regen)
+            self.regen_old(gone, tmp, o, l, er)
+        self.deltas_by_combine(listed, src, tmp, o, l, er)
+
+    def regen_old(self, gone, tmp, o, l, er):
+        R = self.scene.ROWS
+
+        def regen(e):
+            jobs = []
+            for s, c in gone:
+                rows, cnt = e.pattern_rows(er[s].tobytes())
+                ids = e.pattern_survivors(er[s].tobytes())
+                rk = int(er[s, :c].sum())
+                jobs.append(([self.slot(e, s, i, o) for i in ids], [e.adr(R, tmp[(s, c)])],
+                             rows[rk * self.k:(rk + 1) * self.k], 0))
+            return e.combine(jobs, l)
+        self.both("combine(old contents)", regen)
+
+    def deltas_by_combine(self, listed, src, tmp, o, l, er):
+        R, E = self.scene.ROWS, self.model.E
 
         def delta(e):
             jobs = []
@@ -789,7 +1109,7 @@ class Driver:
 
     def undamaged(self, s):
         w = self.wrong(s).any(axis=1)
-        return [c for c in range(self.k) if not self.er[s, c] and not w[c]]
+        return [c for c in range(self.k) if self.L[s] and not self.er[s, c] and not w[c]]
 
     def op_update_plain(self):
         """Some stripes untouched, some with one shard, one with min(k, 3)
@@ -804,11 +1124,14 @@ class Driver:
             cnt = min(self.k, 3, len(ok)) if j == 0 else 1
             listed[s] = sorted(int(c) for c in self.rng.choice(ok, size=cnt, replace=False))
         self.op_update(listed)
-        sl = self.slice_of()
+        s = self.slice_stripe(order)
+        sl = self.slice_of(self.L[s])
         if sl:
-            s = order[-1]
             self.op_update({s: [int(self.rng.choice(self.undamaged(s)))]}, sl=sl)
         return True
+
+    def slice_stripe(self, order):
+        return order[-1]
 
     def op_update_degraded(self):
         """Changed shards present and erased, an erased parity among the
@@ -826,7 +1149,7 @@ class Driver:
         for s in range(self.stripes):
             ok = self.undamaged(s)
             gone = [c for c in range(self.k) if self.er[s, c]] if self.clean(s) and self.e(s) <= self.m else []
-            if s == over:
+            if s == over or not self.L[s]:
                 gone = []
             elif s != keep and not gone and not self.rng.integers(3):
                 continue    # an unlisted stripe
@@ -900,6 +1223,8 @@ class Driver:
         present shards are always among them."""
         reads = []
         for s in range(self.stripes):
+            if not self.L[s]:
+                continue
             gone = [int(i) for i in np.flatnonzero(self.er[s])] if self.e(s) <= self.m else []
             bad = [int(i) for i in np.flatnonzero(self.wrong(s).any(axis=1))]
             pres = [int(i) for i in np.flatnonzero(self.er[s] == 0)]
@@ -909,20 +1234,27 @@ class Driver:
             reads += [(s, i) for i in sorted(take)]
         reads = reads[:NROWS // 2]
         got = self.read(reads, 0, self.S)
-        sl = self.slice_of()
-        if sl:
-            self.read(reads[:4], *sl)
+        self.slice_read(reads)
         self.ledger["read"] += 1
         return got
 
+    def slice_read(self, reads):
+        sl = self.slice_of()
+        if sl:
+            self.read(reads[:4], *sl)
+
     def read(self, reads, o, l):
-        offs, R, fl = self.rows(len(reads)), self.scene.ROWS, self.flags()
+        offs = self.rows(len(reads))
+        self.call_read(reads, offs, o, l)
+        return [(s, i, off) for (s, i), off in zip(reads, offs) if self.er[s, i]]
+
+    def call_read(self, reads, offs, o, l):
+        R, fl = self.scene.ROWS, self.flags()
         if not self.ptrs:
             self.both("read_stripes", lambda e: e.read_stripes(
                 *self.sargs(e, o, l), fl, [(s, i, e.adr(R, off)) for (s, i), off in zip(reads, offs)]))
         else:
             self.by_rows(reads, offs, o, l, "combine(read)")
-        return [(s, i, off) for (s, i), off in zip(reads, offs) if self.er[s, i]]
 
     def by_rows(self, reads, offs, o, l, name):
         """rs_combine's decode-row form: "a holder of some survivors of a
@@ -955,18 +1287,25 @@ class Driver:
             self.both("pattern_survivors", lambda e: list(e.pattern_survivors(fl)))
         reads = [(s, i) for s, i, _ in regenerated]
         offs = self.rows(len(reads))
-        self.by_rows(reads, offs, 0, self.S, "combine(decode rows)")
+        self.rows_again(reads, offs)
         rows = self.model.mem.bufs[self.scene.ROWS]
         for (s, i, a), b in zip(regenerated, offs):
-            assert np.array_equal(rows[a:a + self.S], rows[b:b + self.S]), (self.what(), s, i)
+            assert np.array_equal(rows[a:a + self.L[s]], rows[b:b + self.L[s]]), (self.what(), s, i)
         self.ledger["patterns"] += 1
+
+    def rows_again(self, reads, offs):
+        self.by_rows(reads, offs, 0, self.S, "combine(decode rows)")
+
+    def fit(self, s, chosen, w):
+        """The shards of a scattered damage plan that the scenario can take."""
+        return chosen
 
     def shards_only(self):
         """Where rs_correct_columns refuses the code, only the shard-level scrub repairs."""
         return self.m > 16
 
-    def offsets(self, count):
-        S = self.S
+    def offsets(self, count, S=None):
+        S = self.S if S is None else S
         special = [o for o in dict.fromkeys([0, 15, 16, 4095, 4096, S - 17, S - 1]) if 0 <= o < S]
         pick = [int(special[j]) for j in self.rng.permutation(len(special))[:max(1, count // 2)]]
         pick += [int(x) for x in self.rng.integers(0, S, size=count)]
@@ -980,8 +1319,8 @@ class Driver:
         e) / 2) shards, arbitrary bytes.  A stripe with r - k < 2 gets none."""
         hit = 0
         for s in range(self.stripes):
-            t, er_row = self.t(s), self.er[s]
-            if t < 1 or self.e(s) > self.m:
+            t, er_row, S = self.t(s), self.er[s], self.L[s]
+            if t < 1 or self.e(s) > self.m or not S:
                 continue
             pres = [int(i) for i in np.flatnonzero(er_row == 0)]
             w = self.wrong(s)
@@ -989,19 +1328,20 @@ class Driver:
             if kind == "whole":
                 room = t - int(w.any(axis=1).sum())
                 for i in self.rng.permutation(pres)[:max(0, min(room, 1 + int(self.rng.integers(t))))]:
-                    plan.append((int(i), 0, self.rng.integers(0, 256, size=self.S, dtype=np.uint8)))
+                    plan.append((int(i), 0, self.rng.integers(0, 256, size=S, dtype=np.uint8)))
             else:
                 ids = survivors(er_row, self.k, self.n)
                 comp = [i for i in pres if i not in ids]
                 room = t - int(w.any(axis=1).sum()) if self.shards_only() else min(len(pres), 2 * t + 1)
                 chosen = list(dict.fromkeys([int(self.rng.choice(ids)), int(self.rng.choice(comp))] +
                                             [int(i) for i in self.rng.permutation(pres)]))[:max(0, room)]
+                chosen = self.fit(s, chosen, w)
                 if chosen:
-                    full = self.offsets(1)[0]           # one column filled to the radius
+                    full = self.offsets(1, S)[0]        # one column filled to the radius
                     for i in chosen[:t]:
                         plan.append((i, full, None))
                     for j, i in enumerate(chosen):      # and every shard at offsets of its own
-                        for o in self.offsets(1 + j % 3):
+                        for o in self.offsets(1 + j % 3, S):
                             plan.append((i, o, None))
             col = w.sum(axis=0)
             did = False
@@ -1014,9 +1354,9 @@ class Driver:
                 b, off = self.scene.at(s, i)
                 self.host("xor", b, off + o, mask)
                 did = True
-            if did and kind != "whole" and r16(self.S) > self.S:
+            if did and kind != "whole" and r16(S) > S:
                 b, off = self.scene.at(s, pres[0])
-                self.host("xor", b, off + self.S + int(self.rng.integers(r16(self.S) - self.S)),
+                self.host("xor", b, off + S + int(self.rng.integers(r16(S) - S)),
                           np.array([0x5A], dtype=np.uint8))
             assert self.within(s, self.wrong(s), er_row, self.shards_only())
             hit += did
@@ -1042,29 +1382,34 @@ class Driver:
                     self.er[s] = 0
 
     def op_checked(self):
-        off, fl = self.fbrow(), self.flags()
+        off = self.fbrow()
+        self.call_checked(self.flags(), off)
+        fb = self.verdicts(off)
+        self.settle(fb)
+        self.ledger["checked"] += 1
+        return fb
+
+    def call_checked(self, fl, off):
         if self.ptrs:
             self.both("reconstruct_checked_ptrs",
                       lambda e: e.reconstruct_checked_ptrs(*self.targs(e), fl, e.adr(self.scene.FB, off)))
         else:
             self.both("reconstruct_checked",
                       lambda e: e.reconstruct_checked(*self.sargs(e), fl, e.adr(self.scene.FB, off)))
-        fb = self.verdicts(off)
-        self.settle(fb)
-        self.ledger["checked"] += 1
-        return fb
 
     def op_reconstruct(self):
         if self.m == 0 or not self.er.any():
             return False
-        fl = self.flags()
+        self.call_reconstruct(self.flags())
+        self.settle()
+        self.ledger["reconstruct"] += 1
+        return True
+
+    def call_reconstruct(self, fl):
         if self.ptrs:
             self.both("reconstruct_ptrs", lambda e: e.reconstruct_ptrs(*self.targs(e), fl))
         else:
             self.both("reconstruct_stripes", lambda e: e.reconstruct_stripes(*self.sargs(e), fl))
-        self.settle()
-        self.ledger["reconstruct"] += 1
-        return True
 
     def op_columns(self, unrepairable=True):
         """rs_correct_columns with the flags.  A clean stripe with r - k == 1
@@ -1075,18 +1420,14 @@ class Driver:
         flip = None
         if unrepairable and self.m <= 16:
             for s in range(self.stripes):
-                if self.m - self.e(s) == 1 and self.clean(s):
+                if self.m - self.e(s) == 1 and self.clean(s) and self.L[s]:
                     i = int(self.rng.choice(np.flatnonzero(self.er[s] == 0)))
                     b, off = self.scene.at(s, i)
-                    flip = (s, b, off + self.offsets(1)[0], np.array([self.rng.integers(1, 256)], dtype=np.uint8))
+                    flip = (s, b, off + self.offsets(1, self.L[s])[0], np.array([self.rng.integers(1, 256)], dtype=np.uint8))
                     self.host("xor", *flip[1:])
                     self.ledger["damage"] += 1
                     break
-        if self.ptrs:
-            res = self.both("correct_columns_ptrs", lambda e: e.correct_columns_ptrs(*self.targs(e), erased=fl),
-                            sync=True)
-        else:
-            res = self.both("correct_columns", lambda e: e.correct_columns(*self.sargs(e), erased=fl), sync=True)
+        res = self.call_columns(fl)
         self.ledger["columns"] += 1
         if self.m > 16:
             assert res == ["refused", RS_EINVAL], (self.what(), res)
@@ -1104,6 +1445,12 @@ class Driver:
         for s in range(self.stripes):
             assert self.clean(s), (self.what(), s)
         return res
+
+    def call_columns(self, fl):
+        if self.ptrs:
+            return self.both("correct_columns_ptrs", lambda e: e.correct_columns_ptrs(*self.targs(e), erased=fl),
+                             sync=True)
+        return self.both("correct_columns", lambda e: e.correct_columns(*self.sargs(e), erased=fl), sync=True)
 
     def can_shards(self):
         return (self.m > 0 and not self.ptrs and
@@ -1164,7 +1511,9 @@ class Driver:
             assert (fb == CLEAN).all() and not self.er.any(), (self.what(), fb.tolist())
             if m >= 2:
                 self.op_damage("whole")                                     # 13
+            self.beyond_the_radius()
             self.op_shards()                                                # 14
+            self.other_data()
             self.op_lose(self.skeleton_sets(fewer=True))                    # 15
             if m >= 2:
                 self.op_damage("whole")
@@ -1175,6 +1524,12 @@ class Driver:
             self.op_reconstruct()                                           # 16
         self.finish()                                                       # 17
 
+    def beyond_the_radius(self):
+        pass
+
+    def other_data(self):
+        pass
+
     def finish(self):
         """All clean, every [0, S) the truth, the stored parity the re-encoded data."""
         if self.er.any():
@@ -1183,17 +1538,18 @@ class Driver:
         assert (self.op_verify() == CLEAN).all(), self.what()
         self.checkpoint()
         for s in range(self.stripes):
-            data = np.stack([self.stored(s, c) for c in range(self.k)])
-            assert np.array_equal(data, self.truth[s, :self.k]), (self.what(), s)
+            L = self.L[s]
+            data = np.stack([self.stored(s, c)[:L] for c in range(self.k)])
+            assert np.array_equal(data, self.truth[s, :self.k, :L]), (self.what(), s)
             if self.m:
                 par = np_rs.apply_rows(np_rs.fec_matrix(self.k, self.n)[self.k:], data)
-                stored = np.stack([self.stored(s, i) for i in range(self.k, self.n)])
+                stored = np.stack([self.stored(s, i)[:L] for i in range(self.k, self.n)])
                 assert np.array_equal(par, stored), (self.what(), s)
-                assert np.array_equal(par, self.truth[s, self.k:]), (self.what(), s)
+                assert np.array_equal(par, self.truth[s, self.k:, :L]), (self.what(), s)
 
     def random_walk(self):
         """WALK further ops, drawn from those whose preconditions hold."""
-        kinds = defined_kinds(self.k, self.n, self.ptrs)
+        kinds = self.kinds()
         done = 0
         while done < self.walk:
             kind = kinds[int(self.rng.integers(len(kinds)))]
@@ -1226,13 +1582,18 @@ class Driver:
                 ok = self.op_columns() is not None
             elif kind == "shards":
                 ok = self.op_shards() is not None
-            else:
+            elif kind == "reconstruct":
                 ok = self.op_reconstruct()
+            else:
+                ok = self.op_other(kind)
             done += 1 if ok else 0
         # the final repair
         if any(not self.clean(s) for s in range(self.stripes)):
             self.repair_damage()
         self.finish()
+
+    def kinds(self):
+        return defined_kinds(self.k, self.n, self.ptrs)
 
     def run(self):
         self.in_skeleton = True

@@ -21,6 +21,12 @@ The driver runs with Naive in the engine's place: every scenario must agree,
 end in codewords that equal the remembered truth, and satisfy the coverage
 ledger.  Then thirteen defects are injected into Naive one at a time, and the
 driver must report a mismatch for each in at least one scenario.
+
+The scenarios of store_model_io.py (scattered-shard I/O over a per-call table
+with decoys, a length per stripe, a checksum table kept through the whole
+life) run the same way; for them Naive has the eleven calls they add, its
+CRC-32C bit by bit, and fourteen more defects (14 to 27) that those scenarios
+must report.  The model's own CRC-32C is pinned to RFC 3720 here.
 """
 import struct
 
@@ -29,10 +35,12 @@ import pytest
 
 import np_rs
 import store_model as sm
+import store_model_io as io
 from store_model import CLEAN, RS_EINVAL, RS_ENOT_ENOUGH, RS_ETOO_MANY_ERRORS, RS_OK, Refused
 from strided_image import r16
 
 SCENARIOS = sm.scenarios()
+IO_SCENARIOS = io.scenarios_io()
 MUL = np_rs.MUL
 
 MUTANTS = {
@@ -49,6 +57,21 @@ MUTANTS = {
     11: "one stripe uses the previous call's erasure pattern",
     12: "checked repair fills a slot from the truth",
     13: "rewritten / corrected reported for an erased shard",
+    # the scenarios of store_model_io.py
+    14: "a checksum covers the pad up to 16",
+    15: "the checksum of the last, ragged sector taken over a full sector",
+    16: "the checksum compute writes the row of an erased shard",
+    17: "the checksum check reports the highest bad sector",
+    18: "the checksum check writes a verdict other than clean for an erased shard",
+    19: "correct_crc32c regenerates from survivors chosen for X, not X + B",
+    20: "correct_crc32c skips the second check",
+    21: "update_ptrs ignores offset for the parity slots",
+    22: "update_ptrs reads an unlisted data entry",
+    23: "read_ptrs writes the slot the table names, not dst",
+    24: "a _lens call treats stripe s at the length of stripe s - 1",
+    25: "a _lens call compares bytes in [L, round_up(L, 16))",
+    26: "a zero-length stripe gets first_bad 0",
+    27: "shard_lens read after the call returned",
 }
 
 
@@ -84,19 +107,27 @@ class Naive(sm.HostEngine):
         self.V = np_rs.vandermonde(n, k)
         self.X = [np_rs.point(i) for i in range(n)]
         self.mutant, self.prev, self.truth, self.inverses = mutant, None, None, {}
+        self.pending = []
 
     # ---- arithmetic ------------------------------------------------------------
     def strided(self, data, dss, parity, pss, pitch):
         def slot(s, i):
             base, stride, j = (data, dss, i) if i < self.k else (parity, pss, i - self.k)
             return base + stride * s + pitch * j
+        slot.table = False
         return slot
 
     def table(self, tab, stripes):
         entries = struct.unpack(f"<{stripes * self.n}q", bytes(self.mem.view(tab, 8 * stripes * self.n)))
-        return lambda s, i: entries[s * self.n + i]
+        self.flush()
+
+        def slot(s, i, offset=0):
+            return entries[s * self.n + i] + offset
+        slot.table = True
+        return slot
 
     def flags(self, erased, stripes):
+        self.flush()
         er = np.array([[1 if erased is not None and erased[s * self.n + i] else 0 for i in range(self.n)]
                        for s in range(stripes)], dtype=np.uint8).reshape(stripes, self.n)
         if self.mutant == 11 and self.prev is not None and self.prev.shape == er.shape:
@@ -168,18 +199,21 @@ class Naive(sm.HostEngine):
         return word if int((word[ids] != np.asarray(y)).sum()) <= t else None
 
     def word(self, slot, s, er, length, cols):
-        """The codeword at the columns cols, (present ids, [present][cols]) or
-        None: column by column by Berlekamp-Welch; past 64 columns, k shards
-        that were right so far are tried on the rest."""
+        """The codeword at the columns cols, (present ids, [present][cols],
+        the columns without one within the radius, which keep their bytes):
+        column by column by Berlekamp-Welch; past 64 columns, k shards that
+        were right so far are tried on the rest."""
         pres = [i for i in range(self.n) if not er[i]]
         t = (len(pres) - self.k) // 2
         y = np.stack([self.mem.view(slot(s, i), length)[cols] for i in pres])
-        out, left, suspects = np.zeros_like(y), list(range(len(cols))), set()
+        out, left, suspects, lost = np.zeros_like(y), list(range(len(cols))), set(), []
         while left:
             c = left.pop(0)
             w = self.bw(pres, y[:, c], t)
             if w is None:
-                return None
+                out[:, c] = y[:, c]
+                lost.append(c)
+                continue
             out[:, c] = w[pres]
             suspects |= {j for j in range(len(pres)) if out[j, c] != y[j, c]}
             good = [j for j in range(len(pres)) if j not in suspects][:self.k]
@@ -192,7 +226,7 @@ class Naive(sm.HostEngine):
                 if ok[q]:
                     out[:, c] = cand[:, q]
             left = [c for q, c in enumerate(left) if not ok[q]]
-        return pres, out
+        return pres, out, lost
 
     def first_bad(self, slot, s, er, length, limit):
         """(verdict, the columns below limit at which a compared shard differs)."""
@@ -287,10 +321,12 @@ class Naive(sm.HostEngine):
             if self.mutant == 13 and er[s].any():
                 marks[s * self.n + int(np.flatnonzero(er[s])[0])] = 1
             found = self.word(slot, s, er[s], length, cols) if self.m - int(er[s].sum()) >= 2 else None
-            if found is None:
+            if found is None or (found[2] and not by_column):
                 status[s] = RS_ETOO_MANY_ERRORS
                 continue
-            pres, w = found
+            pres, w, lost = found
+            if lost:    # left alone while the others are corrected
+                status[s] = RS_ETOO_MANY_ERRORS
             t = (len(pres) - self.k) // 2
             wrong = [i for j, i in enumerate(pres) if (w[j] != self.mem.view(slot(s, i), length)[cols]).any()]
             if not by_column and len(wrong) > t:
@@ -346,7 +382,10 @@ class Naive(sm.HostEngine):
                 self.mem.view(slot(s, c), R)[:] = new
 
     def read_stripes(self, data, dss, parity, pss, pitch, S, stripes, erased, reads):
-        slot, er, R = self.strided(data, dss, parity, pss, pitch), self.flags(erased, stripes), r16(S)
+        self._read(self.strided(data, dss, parity, pss, pitch), S, self.flags(erased, stripes), reads)
+
+    def _read(self, slot, S, er, reads):
+        R = r16(S)
         for s, i, _ in reads:
             if er[s, i]:
                 self.pick(er[s])
@@ -355,6 +394,8 @@ class Naive(sm.HostEngine):
             if self.mutant == 6 and int(row.sum()) < self.m:
                 row[i] = 1
             if row[i]:
+                if self.mutant == 23 and slot.table:
+                    dst = slot(s, i)
                 self.mem.view(dst, R)[:] = self.shard(self.data_of(slot, s, row, R)[1], i)
             else:
                 self.mem.view(dst, R)[:] = self.mem.view(slot(s, i), R)
@@ -381,6 +422,205 @@ class Naive(sm.HostEngine):
     def pattern_survivors(self, erased):
         return self.pick(np.frombuffer(bytes(erased), dtype=np.uint8))
 
+    # ---- scattered-shard I/O -----------------------------------------------------
+    def moved(self, at, offset, parity_too=True):
+        def slot(s, i):
+            return at(s, i) + (offset if i < self.k or parity_too else 0)
+        slot.table = True
+        return slot
+
+    def encode_ptrs(self, tab, S, stripes):
+        slot = self.table(tab, stripes)
+        for s in range(stripes if self.m and S else 0):
+            d = np.stack([self.mem.view(slot(s, c), r16(S)) for c in range(self.k)])
+            for i in range(self.k, self.n):
+                self.put(slot(s, i), self.shard(d, i), S)
+
+    def update_ptrs(self, tab, S, stripes, updates, offset=0):
+        slot = self.moved(self.table(tab, stripes), offset, self.mutant != 21)
+        self._update(slot, S, np.zeros((stripes, self.n), dtype=np.uint8), updates)
+        if self.mutant == 22 and S:     # the parity once more, from all k data entries of the table
+            for s in sorted({s for s, _, _ in updates}):
+                d = np.stack([self.mem.view(slot(s, c), r16(S)) for c in range(self.k)])
+                for i in range(self.k, self.n):
+                    self.put(slot(s, i), self.shard(d, i), S)
+
+    def read_ptrs(self, tab, S, stripes, erased, reads, offset=0):
+        self._read(self.moved(self.table(tab, stripes), offset), S, self.flags(erased, stripes), reads)
+
+    # ---- a length per stripe -----------------------------------------------------
+    def flush(self):
+        todo, self.pending = self.pending, []
+        for fn in todo:
+            fn()
+
+    def sync(self):
+        self.flush()
+
+    def snapshot(self):
+        self.flush()
+        return super().snapshot()
+
+    def poke(self, buf, off, data):
+        self.flush()
+        super().poke(buf, off, data)
+
+    def xor(self, buf, off, data):
+        self.flush()
+        super().xor(buf, off, data)
+
+    def lens_of(self, tab, shard_lens, stripes, erased):
+        er, at = self.flags(erased, stripes), self.table(tab, stripes)
+        for s in range(stripes):
+            self.pick(er[s])
+        lens = [int(shard_lens[s]) for s in range(stripes)]
+        if self.mutant == 24:
+            lens = lens[:1] + lens[:-1]
+        return lens, er, at
+
+    def alone(self, at, s):
+        def slot(_, i):
+            return at(s, i)
+        slot.table = True
+        return slot
+
+    def empty(self, first_bad, s):
+        self.mem.view(first_bad + 4 * s, 4).view(np.uint32)[0] = 0 if self.mutant == 26 else CLEAN
+
+    def verify_ptrs_lens(self, tab, shard_lens, stripes, first_bad, erased=None):
+        if self.mutant == 27:
+            # the work happens when the stream gets to it, and reads the lengths
+            # then: lengths no call accepts leave everything unwritten
+            self.flags(erased, stripes)
+            flags = None if erased is None else bytes(erased)
+
+            def later():
+                if all(int(x) < 1 << 32 for x in shard_lens):
+                    self.mutant = 0
+                    self.verify_ptrs_lens(tab, shard_lens, stripes, first_bad, flags)
+                    self.mutant = 27
+            self.pending.append(later)
+            return
+        lens, er, at = self.lens_of(tab, shard_lens, stripes, erased)
+        for s in range(stripes if any(lens) else 0):
+            if not lens[s]:
+                self.empty(first_bad, s)
+                continue
+            limit = r16(lens[s]) if self.mutant == 25 else lens[s]
+            self.mem.view(first_bad + 4 * s, 4).view(np.uint32)[0] = self.first_bad(at, s, er[s], limit, limit)[0]
+
+    def reconstruct_checked_ptrs_lens(self, tab, shard_lens, stripes, erased, first_bad):
+        lens, er, at = self.lens_of(tab, shard_lens, stripes, erased)
+        for s in range(stripes if any(lens) else 0):
+            if lens[s]:
+                self._rebuild(self.alone(at, s), lens[s], 1, er[s:s + 1], first_bad + 4 * s)
+            else:
+                self.empty(first_bad, s)
+
+    def correct_columns_ptrs_lens(self, tab, shard_lens, stripes, erased=None):
+        lens, er, at = self.lens_of(tab, shard_lens, stripes, erased)
+        status, marks = [], []
+        for s in range(stripes):
+            st, mk = self._scrub(self.alone(at, s), lens[s] if self.m else 0, 1, er[s:s + 1], True)
+            status += st
+            marks += mk
+        return status, marks
+
+    # ---- sector checksums --------------------------------------------------------
+    CRCS = {}
+
+    def crc(self, message):
+        """CRC-32C bit by bit: the message's bits, lowest first, through the
+        reflected polynomial."""
+        key = bytes(message)
+        if key not in self.CRCS:
+            if len(self.CRCS) > 4096:
+                self.CRCS.clear()
+            c = 0xFFFFFFFF
+            for byte in key:
+                c ^= byte
+                for _ in range(8):
+                    c = (c >> 1) ^ 0x82F63B78 if c & 1 else c >> 1
+            self.CRCS[key] = c ^ 0xFFFFFFFF
+        return self.CRCS[key]
+
+    def sums(self, addr, S, sector):
+        out = []
+        for lo in range(0, S, sector):
+            hi = min(lo + sector, S)
+            if hi == S and self.mutant == 14:
+                hi = min(lo + sector, r16(S))
+            if hi == S and self.mutant == 15:
+                hi = min(lo + sector, r16(S) + 32)
+            out.append(self.crc(self.mem.view(addr + lo, hi - lo)))
+        return out
+
+    def entries(self, crcs, x, crc_pitch, count):
+        return self.mem.view(crcs + 4 * x * crc_pitch, 4 * count).view(np.uint32)
+
+    def crc_store(self, slot, S, stripes, er, sector, crcs, crc_pitch):
+        for s in range(stripes if S else 0):
+            for i in range(self.n):
+                if not er[s, i] or self.mutant == 16:
+                    c = self.sums(slot(s, i), S, sector)
+                    self.entries(crcs, s * self.n + i, crc_pitch, len(c))[:] = c
+
+    def bad_sectors(self, addr, S, sector, crcs, x, crc_pitch):
+        c = self.sums(addr, S, sector)
+        return [j for j, (a, b) in enumerate(zip(c, self.entries(crcs, x, crc_pitch, len(c)))) if a != int(b)]
+
+    def crc_check(self, slot, S, stripes, er, sector, crcs, crc_pitch, first_bad):
+        out = self.mem.view(first_bad, 4 * stripes * self.n).view(np.uint32) if S and stripes else []
+        for x in range(len(out)):
+            s, i = divmod(x, self.n)
+            if er[s, i]:
+                out[x] = 0 if self.mutant == 18 else CLEAN
+                continue
+            bad = self.bad_sectors(slot(s, i), S, sector, crcs, x, crc_pitch)
+            out[x] = CLEAN if not bad else bad[-1] if self.mutant == 17 else bad[0]
+
+    def crc32c_stripes(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, erased=None):
+        self.crc_store(self.strided(data, dss, parity, pss, pitch), S, stripes, self.flags(erased, stripes), sector,
+                       crcs, crc_pitch)
+
+    def crc32c_ptrs(self, tab, S, stripes, sector, crcs, crc_pitch, erased=None):
+        self.crc_store(self.table(tab, stripes), S, stripes, self.flags(erased, stripes), sector, crcs, crc_pitch)
+
+    def crc32c_check_stripes(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, first_bad,
+                             erased=None):
+        self.crc_check(self.strided(data, dss, parity, pss, pitch), S, stripes, self.flags(erased, stripes), sector,
+                       crcs, crc_pitch, first_bad)
+
+    def crc32c_check_ptrs(self, tab, S, stripes, sector, crcs, crc_pitch, first_bad, erased=None):
+        self.crc_check(self.table(tab, stripes), S, stripes, self.flags(erased, stripes), sector, crcs, crc_pitch,
+                       first_bad)
+
+    def correct_crc32c(self, data, dss, parity, pss, pitch, S, stripes, sector, crcs, crc_pitch, erased=None):
+        slot, er = self.strided(data, dss, parity, pss, pitch), self.flags(erased, stripes)
+        status, rewritten = [RS_OK] * stripes, [0] * (stripes * self.n)
+        bad = {s: [i for i in range(self.n) if not er[s, i] and
+                   self.bad_sectors(slot(s, i), S, sector, crcs, s * self.n + i, crc_pitch)]
+               for s in range(stripes if S else 0)}
+        if any(b and int(er[s].sum()) > self.m for s, b in bad.items()):
+            raise Refused(RS_ENOT_ENOUGH)
+        for s, b in bad.items():
+            if not b:
+                continue
+            if int(er[s].sum()) + len(b) > self.m:
+                status[s] = RS_ETOO_MANY_ERRORS
+                continue
+            gone = er[s].copy()
+            if self.mutant != 19:
+                gone[b] = 1
+            data_rows = self.data_of(slot, s, gone, r16(S))[1]
+            for i in b:
+                self.put(slot(s, i), self.shard(data_rows, i), S)
+                rewritten[s * self.n + i] = 1
+            if self.mutant != 20 and any(self.bad_sectors(slot(s, i), S, sector, crcs, s * self.n + i, crc_pitch)
+                                         for i in b):
+                status[s] = RS_ETOO_MANY_ERRORS
+        return status, bytes(rewritten)
+
 
 # The naive engine is slow where k * S is large: those scenarios run at a
 # reduced S here (one that is as ragged), never 16, 17 or 4112, and in the
@@ -393,7 +633,7 @@ def slow(scenario):
 
 
 def run(scenario, gran, mutant=0):
-    ident, k, n, S, stripes, placement, seed = scenario
+    ident, k, n, S = scenario[:4]
     if slow(scenario):
         S = REDUCED.get(S, S)
     holder = {}
@@ -401,7 +641,7 @@ def run(scenario, gran, mutant=0):
     def make(k, n, names, arrays):
         holder["e"] = Naive(k, n, sm.Memory(names, arrays, bases=[(b + 5) << 40 for b in range(len(arrays))]), mutant)
         return holder["e"]
-    d = sm.Driver(make, k, n, S, stripes, placement, seed, gran, ident=("cpu", ident, gran, mutant))
+    d = io.driver(make, scenario, gran, ("cpu", ident, gran, mutant), S=S)
     holder["e"].truth = lambda s, i: d.truth[s, i]
     return d.run()
 
@@ -420,6 +660,49 @@ def test_agreement_invariants_and_ledger(scenario, gran):
     sm.check_ledger(("cpu", ident, gran, 0), k, n, stripes, placement == "ptrs")
 
 
+@pytest.mark.parametrize("scenario,gran",
+                         [(x, g) for x in IO_SCENARIOS for g in ("every", "async") if g == "every" or not slow(x)],
+                         ids=lambda v: v[0] if isinstance(v, tuple) else v)
+def test_io_agreement_invariants_and_ledger(scenario, gran):
+    """The same for the scenarios of store_model_io.py.  Agreement of the
+    checksum verdicts with "differs from what was written" (asserted by the
+    driver at every crc_check and crc_repair) also proves that the committed
+    seeds meet no CRC collision; the ledger bounds the stripes the repair by
+    checksum had to leave out."""
+    d = run(scenario, gran)
+    assert not d.er.any()
+    full = scenario if not slow(scenario) else scenario[:3] + (REDUCED.get(scenario[3], scenario[3]),) + scenario[4:]
+    io.check_ledger_io(("cpu", scenario[0], gran, 0), full)
+
+
+def test_model_crc32c_is_rfc3720():
+    """The model's CRC-32C is its own; pinned to the RFC's check value, the
+    empty message, and the project's host reference on random lengths."""
+    import rsmi
+    assert sm.crc32c(b"123456789") == 0xE3069283
+    assert sm.crc32c(b"") == 0
+    rng = np.random.default_rng(32)
+    msgs = [rng.integers(0, 256, size=int(x), dtype=np.uint8).tobytes()
+            for x in [0, 1, 70000] + list(rng.integers(0, 70001, size=13))]
+    rows = np.zeros((len(msgs), 70000), dtype=np.uint8)
+    for r, x in enumerate(msgs):
+        rows[r, :len(x)] = np.frombuffer(x, dtype=np.uint8)
+    assert sm.crc32c_rows(rows, [len(x) for x in msgs]).tolist() == list(rsmi.crc32c_host(msgs))
+    assert Naive.crc(Naive, b"123456789") == 0xE3069283 and Naive.crc(Naive, b"") == 0
+
+
+def test_io_scenarios_cover_the_shapes():
+    shapes = {(x[3], x[7]) for x in IO_SCENARIOS}
+    assert {(17, 512), (16, 512), (4112, 4096), (5000, 512), (12328, 4096), (4096, 65536)} <= shapes
+    lens = [x[8] for x in IO_SCENARIOS if x[5] == "ptrs_lens" and not x[0].startswith("io-seed")]
+    assert any(0 in L[1:-1] and all(L[j - 1] and L[j + 1] for j in range(1, len(L) - 1) if not L[j]) for L in lens)
+    assert any(len(set(L)) == 1 for L in lens)
+    assert any(L[0] == max(L) > max(L[1:]) for L in lens) and any(L[-1] == max(L) > max(L[:-1]) for L in lens)
+    assert all(x[2] - x[1] <= 16 for x in IO_SCENARIOS if x[5] == "ptrs_lens")
+    assert len([x for x in IO_SCENARIOS if x[0].startswith("io-seed")]) == 4
+    assert not {x[0] for x in IO_SCENARIOS} & {x[0] for x in SCENARIOS}
+
+
 def test_scenarios_cover_the_sizes_and_codes():
     assert {x[3] for x in SCENARIOS} == set(sm.SIZES)
     for shapes in sm.FIXED.values():
@@ -432,16 +715,19 @@ def test_scenarios_cover_the_sizes_and_codes():
 # The scenarios a mutant is tried on, cheapest first; it is caught when the
 # driver reports a mismatch for any of them.
 MUTANT_SCENARIOS = [x for x in SCENARIOS if x[1] <= 13 and x[3] <= 5000]
+IO_MUTANT_SCENARIOS = sorted([x for x in IO_SCENARIOS if x[1] <= 13 and x[3] <= 5000], key=lambda x: x[1] * x[3] * x[4])
 
 
 @pytest.mark.parametrize("mutant", sorted(MUTANTS),
                          ids=[f"{q}-{MUTANTS[q].replace(' ', '_')}" for q in sorted(MUTANTS)])
 def test_mutant_is_caught(mutant):
     caught = []
-    for scenario in MUTANT_SCENARIOS:
+    tried = MUTANT_SCENARIOS if mutant <= 13 else IO_MUTANT_SCENARIOS
+    for scenario in tried:
         try:
-            run(scenario, "every", mutant)
+            run(scenario, "async" if mutant == 27 else "every", mutant)
         except sm.Mismatch as x:
             caught.append((scenario[0], str(x)[:200]))
             break
-    assert caught, f"mutant {mutant} ({MUTANTS[mutant]}) survived {len(MUTANT_SCENARIOS)} scenarios"
+    print(caught)
+    assert caught, f"mutant {mutant} ({MUTANTS[mutant]}) survived {len(tried)} scenarios"
